@@ -11,7 +11,15 @@ resident in HBM.  Consecutive batches go to --engines engine instances (default 
 stream and work buffers, so one batch's HBM-bound k_prep and small tail launches overlap another batch's
 FP64-bound Brent kernel (the host waits on an engine only before giving it its next batch).
 
-Roofline: the dominant kernel is k_brent (the Brent allele-frequency maximisation), which is FP64-VALU bound
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline figure needs and no more: it sets up,
+warms up, times the N steps and prints the line with `value` and `ms_per_step` (wall milliseconds per timed step),
+the workload description and the section counters of the timed region.  `--full` adds everything else described
+below: the one-engine calibration pass with the `roofline*` sections it feeds, and the `cpu_baseline` leg.
+`--dump-outputs DIR` writes what the last timed step computed -- the per-site results and the genotype rows the
+caller of that step receives -- as DIR/<name>.npy (dump_outputs below); the inputs depend on the arguments alone, so
+two builds can be compared file for file.
+
+Roofline (--full): the dominant kernel is k_brent (the Brent allele-frequency maximisation), which is FP64-VALU bound
 (SURVEY 8(d)).  `roofline` is that FP64 roofline: the SURVEY 8(d) algorithmic op count (nuclear families:
 evals x (19 nFam + 17) + items x nFam x (18 + 36 K); extended families: the per-evaluation peel op counts of
 their schedules) over k_brent's own kernel time, against the 39.3 T non-FMA FP64 ops/s of the spec (78.6
@@ -29,7 +37,7 @@ process (before anything touches the GPU) and relays its exit code; the workers 
 the line records `rccl_world`, the world size the counter all-reduce actually ran over.  `--dry-run` runs the
 same launcher and collectives over gloo with no engine (tests/test_cpu_host.py).
 
-cpu_baseline: the clean-room CPU restatement of the reference path (tests/native/build/cpu_polymutt: the
+cpu_baseline (--full): the clean-room CPU restatement of the reference path (tests/native/build/cpu_polymutt: the
 product host driver over the oracle, with the reference's OpenMP sections over the allele configurations) on
 bounded GLF slices of the same workload, timed on the box's host cores at 1 thread and at the box's CPU share,
 best of 3 -- rank 0, N=1 only.  Two slice sizes give the steady per-site rate with start-up (pedigree load,
@@ -67,8 +75,15 @@ def parse():
                          "one rank (exercises the multi-GPU collective path on a one-GPU box)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher + collectives only (gloo, no engine, no GPU): checks the multi-process path")
-    ap.add_argument("--steps", type=int, default=400)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=400, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the one-engine calibration pass and the roofline sections "
+                         "it feeds (--calib-steps) and the cpu_baseline leg (--cpu-sites, --cpu-reps, --no-cpu-baseline); "
+                         "a plain run sets up, warms up, times --steps steps and prints value and ms_per_step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (per-site results and genotype "
+                         "rows, a fixed seeded sample of them; rank 0's shard) as DIR/<name>.npy")
     ap.add_argument("--families", type=int, default=1000)
     ap.add_argument("--shape", choices=["quad", "trio", "ext10", "extmix", "mixed"], default="quad",
                     help="quad/trio: BASELINE configs 2-3; ext10: config 4 (3-generation pedigrees, ES peeling), one "
@@ -88,8 +103,8 @@ def parse():
                     help="the two GLF slice sizes of the cpu_baseline (steady rate = their difference over the time difference)")
     ap.add_argument("--cpu-reps", type=int, default=3, help="cpu_baseline: best of this many runs per slice and thread count")
     ap.add_argument("--calib-steps", type=int, default=12,
-                    help="one-engine steps after the timed region that give k_brent's own kernel time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: one-engine steps after the timed region that give k_brent's own kernel time")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its cpu_baseline leg")
     ap.add_argument("--host-inputs", action="store_true",
                     help="PCIe-inclusive variant: blocks start in host memory and results return to the host "
                          "(pm_engine_run); never the headline value")
@@ -271,6 +286,39 @@ def measured_fp64_peak():
     return max(rates) if rates else None   # the faster of mul/add: the conservative (larger) peak
 
 
+DUMP_MAX_SITES = 65536        # --dump-outputs: sites sampled from a larger batch (38 float64 columns: 20 MB)
+DUMP_ROW_BYTES = 24 << 20     # ... and the budget of the sampled genotype rows (8 + 3 x 4 B per person and row)
+
+
+def dump_outputs(directory, res, read_row, n_person, vcf, seed):
+    """--dump-outputs: the last timed step's per-site results (`res`, SITE_DTYPE) and genotype rows as
+    DIR/<name>.npy, float64 (float32 for the rows' small integers).  One file per result field, `evals`, `varllk` and
+    `varfreq` with their 7 configurations as columns; `call_row` is left out (an index into the row buffer, not a
+    value).  A batch above DUMP_MAX_SITES sites is sampled without replacement by a generator seeded with `seed`
+    (`site_index` holds the sites, ascending); of the batch's sites that wrote a record, a seeded sample within
+    DUMP_ROW_BYTES gives the genotype rows `calls_*` [row, person] (`calls_site_index` holds their sites).
+    `read_row(r)` returns row r."""
+    os.makedirs(directory, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    n = len(res)
+    idx = np.sort(rng.choice(n, DUMP_MAX_SITES, replace=False)) if n > DUMP_MAX_SITES else np.arange(n)
+    out = {"site_index": idx}
+    for f in res.dtype.names:
+        if f != "call_row":
+            out[f] = res[f][idx]
+    em = np.flatnonzero((res["emit"] == 1) & (res["call_row"] >= 0))
+    max_rows = max(1, DUMP_ROW_BYTES // (20 * n_person))
+    if len(em) > max_rows:
+        em = np.sort(rng.choice(em, max_rows, replace=False))
+    rows = [read_row(int(res["call_row"][s])) for s in em]
+    out["calls_site_index"] = em
+    for f in ("best", "gq", "label") + (() if vcf else ("dosage",)):
+        col = np.array([r[f] for r in rows]).reshape(len(rows), n_person)
+        out["calls_" + f] = col.astype(np.float64 if f == "dosage" else np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
 def launch_workers(args):
     """`bench.py --gpus N` (N > 1) run directly: one worker process per GPU under torch.distributed.run, started
     as a child before this process touches the GPU; rank 0's JSON line reaches our stdout unchanged."""
@@ -330,7 +378,14 @@ def main():
         dist.init_process_group("nccl")
         dev = torch.device("cuda", local)
     import polymutt_amd as pm
-    from polymutt_amd.shard import allreduce_counters, max_over_ranks
+    if dev is not None:
+        from polymutt_amd.shard import allreduce_counters, max_over_ranks
+    else:   # one process, no process group: nothing to combine (and no torch to import)
+        def allreduce_counters(c, device=None):
+            return np.asarray(c, dtype=np.int64)
+
+        def max_over_ranks(v, device=None):
+            return float(v)
 
     kids = {"quad": 2, "trio": 1, "mixed": 2, "ext10": 2, "extmix": 2}[args.shape]
     if args.shape in ("quad", "trio"):
@@ -370,17 +425,26 @@ def main():
                 eng.to_host(href, bufs[p][2], B)
             host.append((hpl, hdm, href))
 
+    dump = args.dump_outputs is not None and rank == 0
+    rsz = pm.engine.SITE_DTYPE.itemsize
+    csz = (pm.engine.VCF_CALL_DTYPE if args.vcf else pm.engine.CALL_DTYPE).itemsize   # device row entry (vcf_mode: 4 B)
+    d_out = (None, None)
+    if dump and host is None:   # the last timed step leaves its results and rows here instead of the engine's own buffers
+        d_out = (eng.alloc(B * rsz), eng.alloc(B * npers * csz))
+        eng.to_device(d_out[0], np.zeros(B * rsz, np.uint8), B * rsz)
+    last_host = [None]
+
     pending = [False] * len(engines)
 
-    def step(i):
+    def step(i, d_res=None, d_calls=None):
         if host is not None:
-            eng.run(*host[i % P])   # H2D inputs, pipeline, D2H results + genotype rows
+            last_host[0] = eng.run(*host[i % P])   # H2D inputs, pipeline, D2H results + genotype rows
             return
         d_pl, d_dm, d_ref = bufs[i % P]
         k = i % len(engines)
         if pending[k]:
             engines[k].sync()   # this engine's previous batch (its stats, Brent status); the others keep running
-        engines[k].run_device(B, d_pl, d_dm, d_ref)
+        engines[k].run_device(B, d_pl, d_dm, d_ref, d_res, d_calls)
         pending[k] = True
 
     def drain():
@@ -403,10 +467,27 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        step(i, *(d_out if i == args.steps - 1 else (None, None)))
     drain()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, dev)
+    if dump and args.steps > 0:
+        if host is None:
+            res = np.zeros(B, pm.engine.SITE_DTYPE)
+            eng.to_host(res, d_out[0], B * rsz)
+            row_dtype = pm.engine.VCF_CALL_DTYPE if args.vcf else pm.engine.CALL_DTYPE
+
+            def read_row(r):
+                row = np.zeros(npers, row_dtype)
+                eng.to_host(row, type(d_out[1])(d_out[1].value + r * npers * csz), npers * csz)
+                return row
+        else:
+            res, calls = last_host[0]
+            read_row = calls.__getitem__
+        dump_outputs(args.dump_outputs, res, read_row, npers, args.vcf, args.seed)
+    for p in d_out:
+        if p is not None:
+            eng.free(p)
     kss = [e.kernel_stats() for e in engines]
     ks = type(kss[0])()
     for f, _ in ks._fields_:
@@ -443,7 +524,7 @@ def main():
     ops = brent_ops(ks)
     # one-engine calibration: k_brent's own launch times (nothing overlaps a launch on a single stream)
     cal = None
-    if args.calib_steps > 0 and host is None:
+    if args.full and args.calib_steps > 0 and host is None:
         e0 = engines[0]
         e0.kernel_stats(reset=True)
         for i in range(args.calib_steps):
@@ -467,7 +548,7 @@ def main():
         out = {
             "metric": "sites/sec (whole node) + achieved HBM GB/s, 1000 quad families",
             "value": value, "unit": "sites/s", "n_gpus": world, "rccl_world": rccl_world, "collective_backend": backend,
-            "steps": args.steps, "warmup": args.warmup,
+            "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"{nf} {args.shape} families, synthetic GLF-shaped sites per SURVEY 8(d) generated in "
@@ -506,7 +587,9 @@ def main():
                          "transitions": int(counters[10]), "transversions": int(counters[11]),
                          "nocall": int(counters[15])},
         }
-        if ep and not fused(ref_st):   # the EP hoisting kernel (es_hoist_wave / es_hoist_jit): ops counted by the schedule compiler
+        if not args.full:   # a plain run: the headline sections only (no pass of their own behind the roofline figures)
+            del out["roofline"], out["roofline_hbm"]
+        if args.full and ep and not fused(ref_st):   # the EP hoisting kernel (es_hoist_wave / es_hoist_jit): ops counted by the schedule compiler
             hs = ref_st
             h_ms = hs.es_hoist_ms / max(1, hs.es_hoist_launches)
             h_ops = hs.es_hoist_ops / max(1, hs.es_hoist_launches)
@@ -518,7 +601,7 @@ def main():
                 "launches": hs.es_hoist_launches, "ms_per_step": hs.es_hoist_ms / max(1, args.calib_steps),
                 "op_model": "FP64 operations of the generated peel (each mul, add or fma one), per family shape and "
                             "variant, times the hoisted (item, family) pairs"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args)
             out["cpu_baseline"] = cb
             if cb and "value" in cb:   # against the faster of the port and the reference-equivalent rate

@@ -10,9 +10,21 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 EXAMPLE = os.path.join(ROOT, "tests", "golden", "example")
 
 
+def _raise_open_file_limit():
+    """The GLF readers (the product's and the CPU driver's, as the reference's) hold one open file per person, 2000
+    and more in the big fixtures: lift the soft RLIMIT_NOFILE (1024 for an ordinary login) to the hard limit for this
+    process and the programs the tests start from it."""
+    import resource
+    soft, hard = resource.getrlimit(resource.RLIMIT_NOFILE)
+    want = 65536 if hard == resource.RLIM_INFINITY else hard
+    if soft != resource.RLIM_INFINITY and soft < want:
+        resource.setrlimit(resource.RLIMIT_NOFILE, (want, hard))
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (HIP device); run with -m gpu")
     config.addinivalue_line("markers", "slow: longer CPU test")
+    _raise_open_file_limit()
 
 
 def _gpu_available():

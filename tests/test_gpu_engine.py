@@ -430,13 +430,55 @@ def test_bench_rccl_group_of_one(built):
     collective path of the multi-GPU bench (src/main.cpp:264-282's summary), exercised without a second GPU."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rccl", "--steps", "3", "--warmup", "1",
-                        "--batch", "8192", "--calib-steps", "1", "--no-cpu-baseline"], capture_output=True, text=True,
+                        "--batch", "8192", "--full", "--calib-steps", "1", "--no-cpu-baseline"], capture_output=True, text=True,
                        timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     print("collective_backend:", line["collective_backend"], "rccl_world:", line["rccl_world"])
     assert line["collective_backend"] == "nccl" and line["rccl_world"] == 1
     assert line["counters"]["sites"] == 3 * 8192 and line["value"] > 0
+
+
+@pytest.mark.parametrize("denovo", [True, False])
+def test_bench_plain_line_and_dump_outputs(built, tmp_path, denovo):
+    """A plain bench.py run times exactly --steps steps and prints the headline line without the --full sections;
+    --dump-outputs writes what its last timed step computed: every file equals, bit for bit, the field of
+    pm_engine_run's results on the same sites (the synthetic block of that step, generated on the host), and the
+    sampled genotype rows equal that run's rows."""
+    import json
+    import bench
+    fam, B, steps, pool = 200, 2048, 5, 3   # (the last step takes the pool's second batch, on the first engine)
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                        "--families", str(fam), "--batch", str(B), "--pool", str(pool), "--engines", "2", "--dump-outputs", str(d)]
+                       + ([] if denovo else ["--no-denovo"]), capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and line["counters"]["sites"] == steps * B and line["full"] is False
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 / B - 1) < 1e-9
+    assert line["unit"] == "sites/s" and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert not [k for k in line if k.startswith("roofline")] and not line.get("cpu_baseline")
+    ped = bench.nuclear_pedigree(pm, fam, 2)
+    pl, dm, ref = pm.synth_block_host(ped, B, 7, ((steps - 1) % pool) * B)   # the last timed step's batch
+    eng = pm.Engine(ped, pm.Params.defaults(denovo=1 if denovo else 0), max_batch=B)
+    res, calls = eng.run(pl, dm, ref)
+    eng.close()
+    files = sorted(f[:-4] for f in os.listdir(d))
+    fields = [f for f in pm.engine.SITE_DTYPE.names if f != "call_row"]
+    assert files == sorted(fields + ["site_index", "calls_site_index", "calls_best", "calls_gq", "calls_label", "calls_dosage"])
+    got = {f: np.load(d / (f + ".npy")) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+    assert (got["site_index"] == np.arange(B)).all()
+    for f in fields:
+        assert got[f].tobytes() == res[f].astype(np.float64).tobytes(), f
+    sites = got["calls_site_index"].astype(np.int64)
+    written = np.flatnonzero(res["emit"] == 1)
+    assert np.array_equal(sites, written) and calls.shape[0] == len(written)
+    if not denovo:
+        assert len(written) > 0   # (--denovo writes a record for few sites: the rows are covered by the plain model)
+    for f in ("best", "gq", "label", "dosage"):
+        assert (got["calls_" + f] == calls[f][res["call_row"][sites]]).all(), f
 
 
 @pytest.mark.parametrize("engines,batch", [(1, 4096), (3, 1000), (2, 257)])

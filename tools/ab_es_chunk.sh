@@ -3,7 +3,7 @@
 # batches) with the coefficient chunk covering a whole batch's items (default) against the former chunk 4 items
 # short of it (PM_ES_CHUNK=65532 / 16380: an empty second chunk per list, one extra hoisting + Brent launch pair).
 set -e
-B="python3 bench.py --no-cpu-baseline --shape ext10 --families 200"
+B="python3 bench.py --full --no-cpu-baseline --shape ext10 --families 200"
 O=gpurun_out/ab_es_chunk.txt
 : > $O
 for rep in 1 2; do

@@ -19,7 +19,7 @@ step() {   # step NAME SECONDS CMD...
   local rc=$?
   if [ $rc -ne 0 ]; then echo "step $name failed rc=$rc" >&2; tail -20 "$OUT/$name.err" >&2; exit $rc; fi
 }
-B="python3 $R/bench.py --no-cpu-baseline --engines 1"
+B="python3 $R/bench.py --full --no-cpu-baseline --engines 1"
 EXT="$B --shape ext10 --families 200 --no-denovo --batch 16384 --steps 8 --calib-steps 4"
 EXTDN="$B --shape ext10 --families 200 --batch 4096 --steps 6 --calib-steps 3"
 QDN="$B --steps 12 --calib-steps 4"

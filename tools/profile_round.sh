@@ -12,7 +12,7 @@ OUT=$R/gpurun_out/prof_$ROUND
 mkdir -p "$OUT"
 echo "revision: $(cat "$R/REVISION" 2>/dev/null || echo unknown)" > "$OUT/revision.txt"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --no-cpu-baseline --steps 40 --calib-steps 4"
+BENCH="python3 $R/bench.py --full --no-cpu-baseline --steps 40 --calib-steps 4"
 ONLY=${PR_ONLY:-}   # PR_ONLY="a b c": run only these steps (a round's passes split over several gpurun calls)
 step() {   # step NAME SECONDS CMD...
   local name=$1 secs=$2; shift 2
@@ -24,7 +24,7 @@ step() {   # step NAME SECONDS CMD...
 }
 step fp64_peak 120 "$R/tools/fp64_peak"
 # the default bench line itself (with its cpu_baseline leg), as the driver runs it
-step bench 600 python3 $R/bench.py
+step bench 600 python3 $R/bench.py --full
 # default bench (3 overlapping engines): whole-step kernel mix; per-kernel durations there include GPU sharing
 step trace 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- $BENCH
 # one engine: each kernel alone on the GPU -- the per-kernel times the roofline uses
@@ -56,7 +56,7 @@ step pmc_cfg5_fetch 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/
 # config 4 at its 8-12-member range (extmix), one engine
 step trace_extmix 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_extmix" -o run -- $BENCH --engines 1 --shape extmix --families 200 --batch 16384 --no-denovo --steps 8
 # the other BASELINE configs' bench lines (default three engines)
-B="python3 $R/bench.py --no-cpu-baseline"
+B="python3 $R/bench.py --full --no-cpu-baseline"
 step cfg2 300 $B --shape trio --families 1000 --no-denovo --steps 100
 step cfg4 300 $B --shape ext10 --families 200 --no-denovo --batch 16384 --steps 30
 step cfg4dn 300 $B --shape ext10 --families 200 --batch 4096 --steps 20
