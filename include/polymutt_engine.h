@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define PM_ABI_VERSION 7   /* 7: pm_engine_stuck_site, partial batches on PM_EBRENT; 6: pm_engine_run_vcf; 5: submit / collect */
+#define PM_ABI_VERSION 8   /* 8: per-family de novo evidence (pm_engine_set_denovo_families / pm_engine_denovo_families);
+                               7: pm_engine_stuck_site, partial batches on PM_EBRENT; 6: pm_engine_run_vcf; 5: submit / collect */
 #define PM_NCFG 7           /* varllk slots: 0 mono, 1 ref/ts, 2 ref/tv1, 3 ref/tv2, 4 ts/tv1, 5 ts/tv2, 6 tv1/tv2 */
 
 typedef enum { PM_OK = 0, PM_EINVAL = -1, PM_EHIP = -2, PM_ENOMEM = -3, PM_EBRENT = -4, PM_EPED = -5 } pm_status;
@@ -244,6 +245,34 @@ int pm_engine_collect(pm_engine *eng, pm_site_result *res, pm_geno_call *calls, 
  * finished batch had none.  (core/MathGold.cpp:98,175: the reference exits at that site, its earlier records
  * written.)  The environment variable PM_TEST_ITMAX, read at pm_engine_create, lowers ITMAX (200) for tests. */
 int pm_engine_stuck_site(pm_engine *eng, int32_t *site);
+
+/* Per-family de novo evidence (--denovo engines, not vcf_mode; no reference counterpart: v0.13 prints only the
+ * site-level DQ).  pm_site_result.denovo_lr is a sum over families: for every written record (emit == 1) and family f
+ *   maxidx >= 1:  D_f = log10 L_f^dn(allele1, allele2; varfreq[maxidx]) - log10 L_f^std(allele1, allele2; x_std),
+ *                 x_std = the minimiser of the no-mutation re-optimisation (main.cpp:567-573);
+ *   maxidx == 0:  D_f = log10 L_f^dn(ref, ref == 4 ? 3 : ref + 1; 1.0) - Sum_{persons of f} (-PL[homoRef] / 10)
+ *                 (MonomorphismLogLikelihood_denovo - MonomorphismLogLikelihood, main.cpp:458, :557-565),
+ * L_f being the family's term of CalcAllFamLogLikelihood in the reference's operation order, so Sum_f D_f = denovo_lr
+ * up to summation rounding.  One extra kernel per batch (k_fam_dnlr) over the written rows only; results are
+ * deterministic (fixed reduction trees, no floating-point atomics). */
+typedef struct { int32_t fam; int32_t pad; double lr; } pm_fam_lr;   /* 16 bytes; fam = family index in pm_pedigree order */
+
+/* top_k = 0 switches the feature off (the default: nothing is allocated or launched, every output is bit-identical);
+ * 1..8 keeps, per written record, the top_k families ranked by D_f descending, ties by lower family index.
+ * want_all != 0 also keeps the full [max_batch][n_fam] matrix on the device (PM_EINVAL above 1 GiB).
+ * PM_EINVAL: top_k out of range, an engine without denovo, a vcf_mode engine, or a submitted batch not yet collected. */
+int pm_engine_set_denovo_families(pm_engine *eng, int32_t top_k, int32_t want_all);
+
+/* The rows of the last finished batch (after pm_engine_run, pm_engine_collect, or pm_engine_run_device + pm_engine_sync),
+ * indexed by pm_site_result.call_row: top[n_rows][top_k] (entries past n_fam are {fam = -1, lr = 0}), sum[n_rows]
+ * (Sum_f D_f; may be NULL) and all[n_rows][n_fam] (D_f by family; may be NULL, PM_EINVAL when asked for without
+ * want_all).  After PM_EBRENT only the rows before the stuck site are valid, as for the genotype rows. */
+int pm_engine_denovo_families(pm_engine *eng, pm_fam_lr *top, double *sum, double *all);
+
+/* *n_rows = the rows pm_engine_denovo_families writes: the row count the last pm_engine_run / pm_engine_collect
+ * returned (after PM_EBRENT: the rows before the stuck site), or after pm_engine_run_device + pm_engine_sync the
+ * batch's written records (the results with call_row >= 0). */
+int pm_engine_denovo_rows(pm_engine *eng, int32_t *n_rows);
 
 /* Page-locked host memory for pm_engine_submit's inputs and the result rows (H2D/D2H at full PCIe rate). */
 int pm_host_alloc(uint64_t bytes, void **h_ptr);

@@ -107,6 +107,11 @@ struct pm_engine {
   int wall_khz = 100000;                   // wall_clock64() rate (hipDeviceAttributeWallClockRate)
   int* d_row_site = nullptr;
   int* d_row_blk = nullptr;   // k_rows_count: written records per 1024-site block
+  // per-family de novo evidence (pm_engine_set_denovo_families): off (top_k 0) = no buffer, no launch
+  int fam_top_k = 0, fam_grid = 0;
+  int last_rows = 0;          // written rows of the last finished batch (pm_engine_denovo_families)
+  pm_fam_lr* d_fam_top = nullptr;                                      // [max_batch][top_k]
+  double *d_fam_sum = nullptr, *d_fam_all = nullptr, *d_fam_line = nullptr;   // [max_batch], [max_batch][n_fam] | [fam_grid][n_fam]
   unsigned long long* d_counters = nullptr;
   double M_h[100];
   // stats
@@ -314,7 +319,7 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_fam_start, E->d_fam_kind, E->d_fa, E->d_mo, E->d_sex, E->d_units, E->d_lktab, E->d_M, E->d_syn,
                   E->d_pl, E->d_stage, E->d_ref, E->d_dm, E->d_res, E->d_calls, E->d_raw, E->d_minv, E->d_mono, E->d_evals,
                   E->d_items[0], E->d_items[1], E->d_items[2], E->d_counts, E->d_eval_total, E->d_row_site,
-                  E->d_counters, E->d_row_blk, E->d_qctr};
+                  E->d_counters, E->d_row_blk, E->d_qctr, E->d_fam_top, E->d_fam_sum, E->d_fam_all, E->d_fam_line};
   for (void* b : bufs) if (b) hipFree(b);
   for (auto& pl : E->d_jit_slots)
     for (int* b : pl) if (b) hipFree(b);
@@ -1331,6 +1336,14 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
     hipLaunchKernelGGL(k_ab, dim3(E->n_cu * 8), dim3(256), 0, E->stream, A);
     HIP_TRY(hipGetLastError());
   }
+  if (E->fam_top_k > 0) {   // per-family de novo evidence of the written rows (after k_final_dn and k_rows)
+    FamLrArgs F;
+    F.top_k = E->fam_top_k; F.sum = E->d_fam_sum; F.top = E->d_fam_top; F.all = E->d_fam_all; F.line = E->d_fam_line;
+    // (blocks beyond the row count leave at once; the ES instantiation's peel workspace is d_ws, sized for grid_post blocks)
+    const int grid = std::max(1, std::min(E->fam_grid, n));
+    hipLaunchKernelGGL(E->n_ext > 0 ? k_fam_dnlr<true> : k_fam_dnlr<false>, dim3(grid), dim3(256), 0, E->stream, A, F);
+    HIP_TRY(hipGetLastError());
+  }
   return PM_OK;
 }
 
@@ -1382,7 +1395,59 @@ static int finish_batch(pm_engine* E, const int* counts) {
   int rc = collect_stats(E);
   if (rc) return rc;
   E->stuck_site = counts[5] ? counts[6] : -1;
+  E->last_rows = counts[3];
   if (counts[5]) { pm_set_last_error("ScalarMinimizer::Brent got stuck"); return PM_EBRENT; }
+  return PM_OK;
+}
+
+int pm_engine_set_denovo_families(pm_engine* E, int32_t top_k, int32_t want_all) {
+  if (!E || top_k < 0 || top_k > 8) { pm_set_last_error("pm_engine_set_denovo_families: top_k must be 0 (off) or 1..8"); return PM_EINVAL; }
+  if (E->vcf) { pm_set_last_error("pm_engine_set_denovo_families: not available on a vcf_mode engine"); return PM_EINVAL; }
+  if (!E->par.denovo) { pm_set_last_error("pm_engine_set_denovo_families: the engine was created without denovo"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_denovo_families: a submitted batch has not been collected"); return PM_EINVAL; }
+  const size_t nb = (size_t)E->max_batch, nf = (size_t)E->n_fam;
+  if (top_k > 0 && want_all && nb * nf * sizeof(double) > ((size_t)1 << 30)) {
+    char b[256];
+    snprintf(b, sizeof(b), "pm_engine_set_denovo_families: want_all needs max_batch x n_fam x 8 = %zu bytes on the device (limit 1 GiB)",
+             nb * nf * sizeof(double));
+    pm_set_last_error(b);
+    return PM_EINVAL;
+  }
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  E->fam_top_k = 0;
+  E->last_rows = 0;
+  void** bufs[] = {(void**)&E->d_fam_top, (void**)&E->d_fam_sum, (void**)&E->d_fam_all, (void**)&E->d_fam_line};
+  for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+  if (top_k == 0) return PM_OK;
+  E->fam_grid = E->grid_post;
+  int rc;
+  if ((rc = dalloc(&E->d_fam_top, nb * top_k)) || (rc = dalloc(&E->d_fam_sum, nb))) return rc;
+  if (want_all) rc = dalloc(&E->d_fam_all, nb * nf);
+  else rc = dalloc(&E->d_fam_line, (size_t)E->fam_grid * nf);
+  if (rc) return rc;
+  E->fam_top_k = top_k;
+  return PM_OK;
+}
+
+int pm_engine_denovo_rows(pm_engine* E, int32_t* n_rows) {
+  if (!E || !n_rows) { pm_set_last_error("pm_engine_denovo_rows: invalid arguments"); return PM_EINVAL; }
+  *n_rows = E->fam_top_k > 0 ? E->last_rows : 0;
+  return PM_OK;
+}
+
+int pm_engine_denovo_families(pm_engine* E, pm_fam_lr* top, double* sum, double* all) {
+  if (!E || !top) { pm_set_last_error("pm_engine_denovo_families: invalid arguments"); return PM_EINVAL; }
+  if (E->fam_top_k <= 0) { pm_set_last_error("pm_engine_denovo_families: the feature is off (pm_engine_set_denovo_families)"); return PM_EINVAL; }
+  if (all && !E->d_fam_all) { pm_set_last_error("pm_engine_denovo_families: the full matrix needs want_all"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_denovo_families: a submitted batch has not been collected"); return PM_EINVAL; }
+  const size_t rows = (size_t)E->last_rows;
+  if (rows == 0) return PM_OK;
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  HIP_TRY(hipMemcpy(top, E->d_fam_top, sizeof(pm_fam_lr) * rows * E->fam_top_k, hipMemcpyDeviceToHost));
+  if (sum) HIP_TRY(hipMemcpy(sum, E->d_fam_sum, sizeof(double) * rows, hipMemcpyDeviceToHost));
+  if (all) HIP_TRY(hipMemcpy(all, E->d_fam_all, sizeof(double) * rows * E->n_fam, hipMemcpyDeviceToHost));
   return PM_OK;
 }
 
@@ -1446,7 +1511,7 @@ int pm_engine_collect(pm_engine* E, pm_site_result* res, pm_geno_call* calls, in
   const int n = E->pending_n;
   E->pending_n = -1;
   *n_rows = 0;
-  if (n == 0) return PM_OK;
+  if (n == 0) { E->last_rows = 0; return PM_OK; }
   HIP_TRY(hipSetDevice(E->device));
   HIP_TRY(hipStreamSynchronize(E->stream));
   int counts[16];
@@ -1455,6 +1520,7 @@ int pm_engine_collect(pm_engine* E, pm_site_result* res, pm_geno_call* calls, in
   if (rc && rc != PM_EBRENT) return rc;
   memcpy(res, E->h_res, sizeof(pm_site_result) * n);
   *n_rows = rc ? rows_before(res, E->stuck_site) : counts[3];   // PM_EBRENT: the complete sites' rows only
+  E->last_rows = *n_rows;
   const size_t np = E->n_person;
   if (calls && counts[3] > 0) {
     if (E->vcf) {   // 4-B rows on the device (pm_vcf_call), expanded into the caller's pm_geno_call rows
@@ -1490,6 +1556,7 @@ int pm_engine_run_vcf(pm_engine* E, int32_t n, const uint8_t* pl, const uint8_t*
   if (rc && rc != PM_EBRENT) return rc;
   memcpy(res, E->h_res, sizeof(pm_site_result) * n);
   *n_rows = rc ? rows_before(res, E->stuck_site) : counts[3];   // PM_EBRENT: the complete sites' rows only
+  E->last_rows = *n_rows;
   if (calls && counts[3] > 0)   // the device rows as they are (4 B per person)
     HIP_TRY(hipMemcpy(calls, E->d_calls, sizeof(pm_vcf_call) * E->n_person * (size_t)counts[3], hipMemcpyDeviceToHost));
   return rc;
@@ -1499,7 +1566,7 @@ int pm_engine_run(pm_engine* E, int32_t n, const uint8_t* pl, const uint32_t* dm
                   pm_site_result* res, pm_geno_call* calls, int32_t* n_rows) {
   if (!E || n < 0 || n > E->max_batch || !res || !n_rows) { pm_set_last_error("pm_engine_run: invalid arguments"); return PM_EINVAL; }
   *n_rows = 0;
-  if (n == 0) return PM_OK;
+  if (n == 0) { E->last_rows = 0; return PM_OK; }
   if (!on_device) {   // host inputs: submit + collect
     int rc = pm_engine_submit(E, n, pl, dm, ref);
     if (rc) { E->pending_n = -1; return rc; }
@@ -1517,6 +1584,7 @@ int pm_engine_run(pm_engine* E, int32_t n, const uint8_t* pl, const uint32_t* dm
   int counts[16];
   HIP_TRY(hipMemcpy(counts, E->d_counts, sizeof(counts), hipMemcpyDeviceToHost));
   *n_rows = rc ? rows_before(res, E->stuck_site) : counts[3];   // PM_EBRENT: the complete sites' rows only
+  E->last_rows = *n_rows;
   if (calls && counts[3] > 0) {
     if (E->vcf) {
       const size_t nr = np * (size_t)counts[3];

@@ -3302,6 +3302,170 @@ __global__ void __launch_bounds__(1024) k_rows(DevArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_fam_dnlr: the per-family terms of the de novo LR (pm_engine_denovo_families; no reference counterpart -- v0.13
+// prints only their sum, DQ).  denovoLR (main.cpp:557-573) is a difference of two CalcAllFamLogLikelihood values, each
+// a sum over families, so for a written record and family f
+//   maxidx >= 1:  D_f = log10 L_f^dn(a1, a2; varfreq[maxidx]) - log10 L_f^std(a1, a2; minv[7])   (the cfg-7 item's minimiser)
+//   maxidx == 0:  D_f = log10 L_f^dn(ref, next(ref); 1.0) - Sum_{persons of f} (-PL[homoRef] / 10)  (cfg 0's alleles, :458)
+// with L_f formed as k_brent's reference-order (GEN, PRODUCT) path forms it: founder families the product of
+// lkSinglePerson, nuclear families hoist_nuc + d_parent_prior under the objective's prior mode and member sex 0,
+// extended families d_es_lk<10> / d_es_lk<3> (ES instantiation only: the founder / nuclear one keeps everything in
+// registers).  One block per written row at a time, families across lanes in fam_perm order (one code path per
+// stretch of lanes).  Every D_f goes to the row's line of F.all (want_all) or of the block's scratch line, which
+// each thread re-reads only at the entries it wrote itself.  The row's sum and its top_k ranking are block reductions
+// in a fixed tree -- per-thread serial, xor butterfly within a wave, the waves' partials from LDS in wave order -- so
+// the same input gives the same bits on every run; no atomics.
+struct FamLrArgs {
+  int top_k;          // 1..8
+  double* sum;        // [rows]
+  pm_fam_lr* top;     // [rows][top_k]
+  double* all;        // [rows][n_fam], or null
+  double* line;       // [gridDim.x][n_fam] when all is null
+};
+
+// ranking order: larger lr first, ties by lower family index; fam == INT_MAX marks "none"
+__device__ __forceinline__ bool fam_lr_before(double la, int fa, double lb, int fb) {
+  return fa != INT_MAX && (fb == INT_MAX || la > lb || (la == lb && fa < fb));
+}
+
+template <bool ES>
+__global__ void __launch_bounds__(256) k_fam_dnlr(DevArgs A, FamLrArgs F) {
+  __shared__ double s_lk[256];
+  __shared__ double s_M[100];
+  __shared__ double s_red[2][4];
+  __shared__ int s_redf[2][4];
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lk[i] = A.lktab[i];
+  for (int i = threadIdx.x; i < 100; i += blockDim.x) s_M[i] = A.M[i];
+  __syncthreads();
+  const int rows = A.counts[3], np = A.n_person, nf = A.n_fam;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const size_t ws_stride = (size_t)gridDim.x * blockDim.x;
+  double* wsl = ES ? A.ws + (size_t)blockIdx.x * blockDim.x + threadIdx.x : nullptr;
+  (void)wsl; (void)ws_stride;
+  int par = 0;
+  for (int row = blockIdx.x; row < rows; row += gridDim.x) {   // (block-uniform: every thread reaches the barriers)
+    const int site = A.row_site[row];
+    const pm_site_result* R = A.res + site;
+    const uint8_t* pl = A.pl + (size_t)site * np * 10;
+    const int mx = R->maxidx, r = A.ref[site];
+    const bool mono = mx <= 0;
+    ItemCtx I;
+    if (mono) cfg_alleles(0, r, &I.a1, &I.a2);
+    else { I.a1 = R->allele1; I.a2 = R->allele2; }
+    I.g11 = d_gi(I.a1, I.a1); I.g12 = d_gi(I.a1, I.a2); I.g22 = d_gi(I.a2, I.a2);
+    I.sex = 0; I.chrom = A.chrom;
+    const double x_dn = mono ? 1.0 : R->varfreq[mx];
+    const double x_std = mono ? 1.0 : A.minv[site * 8 + 7];
+    const int h = d_gi(r, r);   // homoRef plane (mono rows)
+    // the objective's prior modes (k_brent): de novo items, then the cfg-7 item
+    const int pm_dn = A.n_fam_gt1 ? PR_AUTO : PR_DN_SINGLE;
+    const int pm_std = !A.n_fam_gt1 ? PR_TRIO
+                       : A.chrom == PM_CHR_X ? PR_X : A.chrom == PM_CHR_Y ? PR_Y : A.chrom == PM_CHR_MT ? PR_MT : PR_AUTO;
+    double pp_dn[9], pp_std[9];
+    d_parent_prior(pm_dn, x_dn, pp_dn);
+    d_parent_prior(pm_std, x_std, pp_std);
+    double* line = F.all ? F.all + (size_t)row * nf : F.line + (size_t)blockIdx.x * nf;
+    double part = 0.0;
+    for (int fi = threadIdx.x; fi < nf; fi += blockDim.x) {
+      const int f = A.fam_perm[fi];
+      const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0, kind = A.fam_kind[f];
+      double l_dn = 0.0, l_std = 0.0;
+      if (mono) {   // the family's share of MonomorphismLogLikelihood: -(Sum PL) / 10 from the exact integer sum (k_prep)
+        int s = 0;
+        for (int j = 0; j < n; j++) s += PLB(pl, np, p0 + j, h);
+        l_std = s ? -(double)s / 10 : 0.0;
+      }
+      if (kind == PM_FAM_FOUNDERS) {   // product of lkSinglePerson (:987-1004), normalised per factor
+#pragma unroll
+        for (int md = 0; md < 2; md++) {
+          if (md == 1 && mono) break;
+          const double fq = md == 0 ? x_dn : x_std, gq = 1 - fq;
+          const double P0 = fq * fq, P1 = fq * gq * 2, P2 = gq * gq;
+          double m = 1.0;
+          int e = 0;
+          for (int j = 0; j < n; j++) {
+            const int p = p0 + j, sx = A.sex[p];
+            const double l11 = s_lk[PLB(pl, np, p, I.g11)], l12 = s_lk[PLB(pl, np, p, I.g12)], l22 = s_lk[PLB(pl, np, p, I.g22)];
+            const bool hap = (A.chrom == PM_CHR_X && sx == MALE) || (A.chrom == PM_CHR_Y && sx == MALE) || A.chrom == PM_CHR_MT;
+            if (A.chrom == PM_CHR_Y && sx != MALE) continue;
+            double sp = 0.0;
+            if (hap) sp = sp + l11 * fq + l22 * gq;   // (the het term is l12 = 0 times 0)
+            else sp = sp + l11 * P0 + l12 * P1 + l22 * P2;
+            int e1;
+            m = frexp(m * sp, &e1);
+            e += e1;
+          }
+          const double l = log10(m) + e * 0.30102999566398119521;
+          if (md == 0) l_dn = l; else l_std = l;
+        }
+      } else if (kind == PM_FAM_NUCLEAR) {
+        double cond[9];
+        I.denovo = 1;
+        hoist_nuc<true>(A, I, pl, s_lk, s_M, p0, n, cond);
+        double v = 0.0;   // lkSingleFam :950-955
+#pragma unroll
+        for (int k = 0; k < 9; k++) v += cond[k] * pp_dn[k];
+        l_dn = log10(v);
+        if (!mono) {
+          I.denovo = 0;
+          hoist_nuc<true>(A, I, pl, s_lk, s_M, p0, n, cond);
+          v = 0.0;
+#pragma unroll
+          for (int k = 0; k < 9; k++) v += cond[k] * pp_std[k];
+          l_std = log10(v);
+        }
+      } else if constexpr (ES) {   // Elston-Stewart peel, lane-interleaved HBM workspace (as k_posterior_es)
+        l_dn = log10(d_es_lk<10>(A, f, pl, s_lk, I.g11, I.g12, I.g22, A.chrom, x_dn, -1, -1, wsl, ws_stride));
+        if (!mono) l_std = log10(d_es_lk<3>(A, f, pl, s_lk, I.g11, I.g12, I.g22, A.chrom, x_std, -1, -1, wsl, ws_stride));
+      }
+      const double D = l_dn - l_std;
+      line[f] = D;
+      part += D;
+    }
+    // the row's sum
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+    if (lane == 0) s_red[par][wv] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) F.sum[row] = ((s_red[par][0] + s_red[par][1]) + s_red[par][2]) + s_red[par][3];
+    par ^= 1;
+    // the ranking: round k takes the best entry that comes after round k - 1's in the order
+    double prev_lr = 0.0;
+    int prev_f = -1;
+    for (int k = 0; k < F.top_k; k++) {
+      double bl = 0.0;
+      int bf = INT_MAX;
+      for (int fi = threadIdx.x; fi < nf; fi += blockDim.x) {
+        const int f = A.fam_perm[fi];
+        const double d = line[f];   // (written by this thread above)
+        const bool after = k == 0 ? d == d : (d < prev_lr || (d == prev_lr && f > prev_f));
+        if (after && fam_lr_before(d, f, bl, bf)) { bl = d; bf = f; }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const double ol = __shfl_xor(bl, o, 64);
+        const int of = __shfl_xor(bf, o, 64);
+        if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
+      }
+      if (lane == 0) { s_red[par][wv] = bl; s_redf[par][wv] = bf; }
+      __syncthreads();
+      bl = s_red[par][0]; bf = s_redf[par][0];
+#pragma unroll
+      for (int w = 1; w < 4; w++)
+        if (fam_lr_before(s_red[par][w], s_redf[par][w], bl, bf)) { bl = s_red[par][w]; bf = s_redf[par][w]; }
+      par ^= 1;
+      if (threadIdx.x == 0) {
+        pm_fam_lr o;
+        o.fam = bf == INT_MAX ? -1 : bf; o.pad = 0; o.lr = bf == INT_MAX ? 0.0 : bl;
+        F.top[(size_t)row * F.top_k + k] = o;
+      }
+      if (bf == INT_MAX) { prev_lr = -INFINITY; prev_f = INT_MAX; }   // exhausted: every later round is empty too
+      else { prev_lr = bl; prev_f = bf; }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // synthetic generator: one thread per (site, family)
 __global__ void k_synth(DevArgs A, int n, uint64_t seed, uint64_t off, uint8_t* pl, uint32_t* dm, uint8_t* ref) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -99,6 +99,8 @@ CALL_DTYPE = np.dtype([("dosage", "<f8"), ("best", "<i2"), ("gq", "<i2"), ("labe
 VCF_CALL_DTYPE = np.dtype([("best", "i1"), ("gq", "i1"), ("label", "i1"), ("pad", "i1")])   # pm_vcf_call
 assert SITE_DTYPE.itemsize == C.sizeof(SiteResult) == 240, SITE_DTYPE.itemsize
 assert CALL_DTYPE.itemsize == C.sizeof(GenoCall) == 16
+FAM_LR_DTYPE = np.dtype([("fam", "<i4"), ("pad", "<i4"), ("lr", "<f8")])   # pm_fam_lr
+assert FAM_LR_DTYPE.itemsize == 16
 
 _lib = None
 
@@ -116,6 +118,9 @@ EXPORTS = {
     "pm_engine_submit": (i32, [C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_engine_collect": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, P(i32)]),
     "pm_engine_stuck_site": (i32, [C.c_void_p, P(i32)]),
+    "pm_engine_set_denovo_families": (i32, [C.c_void_p, i32, i32]),
+    "pm_engine_denovo_families": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pm_engine_denovo_rows": (i32, [C.c_void_p, P(i32)]),
     "pm_host_alloc": (i32, [u64, P(C.c_void_p)]),
     "pm_host_free": (i32, [C.c_void_p]),
     "pm_engine_to_planar": (i32, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
@@ -254,6 +259,8 @@ class Engine:
         if rc != 0:
             raise RuntimeError(f"pm_engine_create failed ({rc}): {_err(self.lib)}")
         self.h = h
+        self.n_fam = ped_struct.n_fam
+        self._fam_k, self._fam_all = 0, False
 
     def begin_section(self, chrom=PM_CHR_AUTO):
         self._check(self.lib.pm_engine_begin_section(self.h, chrom))
@@ -349,6 +356,26 @@ class Engine:
         s = KernelStats()
         self._check(self.lib.pm_engine_kernel_stats(self.h, C.byref(s), 1 if reset else 0))
         return s
+
+    def set_denovo_families(self, top_k, want_all=False):
+        """pm_engine_set_denovo_families: keep, per written de novo record, the top_k (1..8; 0 = off) families ranked by
+        their term D_f of the record's DQ, and with want_all the whole [rows, n_fam] matrix."""
+        self._check(self.lib.pm_engine_set_denovo_families(self.h, int(top_k), 1 if want_all else 0))
+        self._fam_k, self._fam_all = int(top_k), bool(want_all) and top_k > 0
+
+    def denovo_families(self):
+        """pm_engine_denovo_families for the last finished batch (run(), collect(), or run_device() + sync()):
+        (top[rows, k] of FAM_LR_DTYPE, sum[rows], all[rows, n_fam] or None), rows indexed by call_row."""
+        if self._fam_k <= 0:
+            raise RuntimeError("denovo_families: the feature is off (set_denovo_families)")
+        n = i32(0)
+        self._check(self.lib.pm_engine_denovo_rows(self.h, C.byref(n)))
+        rows = n.value
+        top = np.zeros((rows, self._fam_k), dtype=FAM_LR_DTYPE)
+        tot = np.zeros(rows, dtype=np.float64)
+        full = np.zeros((rows, self.n_fam), dtype=np.float64) if self._fam_all else None
+        self._check(self.lib.pm_engine_denovo_families(self.h, _ptr(top), _ptr(tot), None if full is None else _ptr(full)))
+        return top, tot, full
 
     def stuck_site(self):
         """pm_engine_stuck_site: the first site of the last finished batch whose Brent hit ITMAX (-1: none)."""

@@ -25,6 +25,9 @@ struct Options {
   int io_threads = 0;   // GLF decode threads (0: min(16, hardware threads))
   std::string blocksIn, blocksOut;   // --in_blocks FILE (.pmb input in place of -g), --glf2blocks FILE (convert)
   int blockSites = 4096;
+  // --denovo_families K: de novo records name the K families (1..8) with the largest share of DQ (INFO tags DNF / DNFLR)
+  int denovo_families = 0;
+  bool denovo_families_given = false;
   std::string cmd;
   pm_params params() const;
 };
@@ -67,6 +70,12 @@ class SiteEvaluator {
     if (d.second >= 0) throw BrentError(d.second, d.first);
     return d.first;
   }
+  // --denovo_families: set_denovo_families(K) once, before the first batch; then denovo_families(top) hands out the
+  // rows [rows][K] (indexed by call_row) of the batch the last run() or collect() returned -- also after that call
+  // threw a BrentError (the rows before the stuck site) -- and must be called before that batch's engine is given
+  // another one.  Only the GPU engine computes them.
+  virtual void set_denovo_families(int top_k) { (void)top_k; throw FatalError("--denovo_families needs the GPU engine\n"); }
+  virtual void denovo_families(pm_fam_lr* top) { (void)top; throw FatalError("--denovo_families needs the GPU engine\n"); }
   // Host memory for the batch buffers (the engine: page-locked, for asynchronous copies)
   virtual void* host_alloc(size_t bytes);
   virtual void host_free(void* p);

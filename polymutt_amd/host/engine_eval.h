@@ -53,6 +53,7 @@ class EngineEvaluator : public SiteEvaluator {
   void run(int n, const uint8_t* pl, const uint32_t* dm, const uint8_t* ref, pm_site_result* res, pm_geno_call* calls,
            int* n_rows) override {
     check(pm_engine_set_posterior_carry(eng_[0], seen_ ? 1 : 0));
+    last_ = eng_[0];
     int rc = pm_engine_run(eng_[0], n, pl, dm, ref, 0, res, calls, n_rows);
     if (rc == PM_EBRENT) throw stuck(eng_[0], *n_rows);
     check(rc);
@@ -93,11 +94,19 @@ class EngineEvaluator : public SiteEvaluator {
     Job j = q_.front();
     q_.pop_front();
     int rows = 0;
+    last_ = j.e;
     int rc = pm_engine_collect(j.e, j.res, j.calls, &rows);
     if (rc == PM_EBRENT) throw stuck(j.e, rows);   // (the driver drains the writer first: no exit() with threads live)
     check(rc);
     note(j.res, j.n);
     return rows;
+  }
+  void set_denovo_families(int top_k) override {
+    for (auto* e : eng_) check(pm_engine_set_denovo_families(e, top_k, 0));
+  }
+  void denovo_families(pm_fam_lr* top) override {   // (the engine that ran the batch last returned: idle until its next submit)
+    if (!last_) throw FatalError("GPU engine error: no finished batch\n");
+    check(pm_engine_denovo_families(last_, top, nullptr, nullptr));
   }
   void* host_alloc(size_t bytes) override {
     void* p = nullptr;
@@ -124,6 +133,7 @@ class EngineEvaluator : public SiteEvaluator {
     return BrentError(k < 0 ? 0 : k, rows);
   }
   std::vector<pm_engine*> eng_;
+  pm_engine* last_ = nullptr;   // the engine whose batch run() / collect() returned last (denovo_families)
   std::deque<Job> q_;
   std::vector<void*> pinned_;
   size_t next_ = 0;

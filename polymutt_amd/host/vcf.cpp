@@ -29,6 +29,10 @@ void VcfWriter::header() {
   fprintf(fh, "##INFO=<ID=MQ,Number=1,Type=Float,Description=\"Average Map Quality\">\n");
   if (!singleNuclear()) fprintf(fh, "##INFO=<ID=AF,Number=.,Type=Float,Description=\"Reference Allele Frequency\">\n");
   if (denovo) fprintf(fh, "##INFO=<ID=DQ,Number=1,Type=Float,Description=\"De Novo Mutation Quality\">\n");
+  if (denovo && dnf_k > 0) {
+    fprintf(fh, "##INFO=<ID=DNF,Number=.,Type=String,Description=\"Families With the Largest Shares of DQ, Largest First\">\n");
+    fprintf(fh, "##INFO=<ID=DNFLR,Number=.,Type=Float,Description=\"Share of DQ (log10 Likelihood Ratio) of Each DNF Family\">\n");
+  }
   fprintf(fh, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n");
   fprintf(fh, "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype Quality\">\n");
   fprintf(fh, "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Read Depth\">\n");
@@ -43,17 +47,17 @@ void VcfWriter::header() {
 }
 
 void VcfWriter::output(const std::string& label, int pos1, int refBase, const pm_site_result& r, const pm_geno_call* calls,
-                       const uint8_t* pl, const uint32_t* dm) {
+                       const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf) {
   if (!header_written) header();
   if (r.emit != 1) return;   // OutputVCF_denovo returns before the record when denovoLR < minLLR (:1868)
   line_.clear();
-  format(line_, label, pos1, refBase, r, calls, pl, dm);
+  format(line_, label, pos1, refBase, r, calls, pl, dm, dnf);
   fwrite(line_.data(), 1, line_.size(), fh);
   fflush(fh);
 }
 
 void VcfWriter::format(std::string& L, const std::string& label, int pos1, int refBase, const pm_site_result& r,
-                       const pm_geno_call* calls, const uint8_t* pl, const uint32_t* dm) const {
+                       const pm_geno_call* calls, const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf) const {
   const int n = (int)ped->column_pid.size();
   const bool refIsA1 = refBase == r.allele1;
   char info[512], head[1024];
@@ -126,9 +130,20 @@ void VcfWriter::format(std::string& L, const std::string& label, int pos1, int r
     if (refIsA1) alt = std::string(1, kBases[a2]);
     else alt = std::string(1, kBases[r.allele1]) + "," + kBases[a2];
     L += label;
-    snprintf(head, sizeof(head), "\t%d\t%s\t%c\t%s\t%d\t%s\t%s\t%s", pos1, ".", kBases[refBase], alt.c_str(), int(r.poly_qual + 0.5), ".",
-             info, gl_off ? "GT:GQ:DP" : "GT:GQ:DP:PL");
+    snprintf(head, sizeof(head), "\t%d\t%s\t%c\t%s\t%d\t%s\t%s", pos1, ".", kBases[refBase], alt.c_str(), int(r.poly_qual + 0.5), ".", info);
     L += head;
+    if (dnf_k > 0 && dnf) {   // ;DNF=<famid>[,...];DNFLR=<%.3f>[,...] (entries past the family count are not printed)
+      std::string ids, lrs;
+      for (int k = 0; k < dnf_k && dnf[k].fam >= 0 && dnf[k].fam < (int)ped->families.size(); k++) {
+        char v[64];
+        snprintf(v, sizeof(v), "%.3f", dnf[k].lr);
+        if (k) { ids += ','; lrs += ','; }
+        ids += ped->families[dnf[k].fam].famid;
+        lrs += v;
+      }
+      if (!ids.empty()) { L += ";DNF="; L += ids; L += ";DNFLR="; L += lrs; }
+    }
+    L += gl_off ? "\tGT:GQ:DP" : "\tGT:GQ:DP:PL";
     const size_t at = L.size();
     L.resize(at + (size_t)n * 96 + 2);
     char* o = &L[at];

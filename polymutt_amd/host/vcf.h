@@ -18,15 +18,17 @@ struct VcfWriter {
   bool gl_off = false, force_call = false, denovo = false;
   bool header_written = false;
   int chrom = PM_CHR_AUTO;
+  int dnf_k = 0;               // --denovo_families K: INFO gains DNF (family ids) and DNFLR (their shares of DQ) after DQ
 
   // One OutputVCF(_denovo) call: writes the header on first use, then the record unless suppressed.
+  // dnf: the record's dnf_k ranked families (pm_engine_denovo_families; required when dnf_k > 0)
   void output(const std::string& label, int pos1, int refBase, const pm_site_result& r, const pm_geno_call* calls,
-              const uint8_t* pl, const uint32_t* dm);
+              const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf = nullptr);
   void header();   // written by output() on first use; a sharded run's lead writes it once at the merge
   // The record text of an emitted site (r.emit == 1) appended to `out`, as output() writes it (no header, no I/O;
   // safe to call from several threads at once: the pipelined CLI formats a batch's records in parallel)
   void format(std::string& out, const std::string& label, int pos1, int refBase, const pm_site_result& r,
-              const pm_geno_call* calls, const uint8_t* pl, const uint32_t* dm) const;
+              const pm_geno_call* calls, const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf = nullptr) const;
 
  private:
   bool singleNuclear() const;

@@ -1,0 +1,52 @@
+"""Device-free checks of the per-family de novo evidence: the CLI's argument errors (raised while the command line is
+parsed: before the pedigree is read or an engine created), ABI 8 and the pm_fam_lr layout, and the register-resident
+founder / nuclear instantiation of k_fam_dnlr read from the built gfx950 code object."""
+import ctypes as C
+import os
+import subprocess
+
+import pytest
+
+import polymutt_amd as pm
+from conftest import EXAMPLE
+from test_cpu_kernel_resources import _resources
+
+BASE = ["-p", "test.ped", "-d", "test.dat", "-g", "test.gif", "--out_vcf"]
+
+
+@pytest.mark.parametrize("extra,message", [
+    (["--denovo_families", "2"], "--denovo_families needs --denovo"),
+    (["--denovo", "--in_vcf", "testvcf.in.vcf.gz", "--denovo_families", "2"], "--denovo_families is not available with --in_vcf"),
+    (["--denovo", "--denovo_families", "0"], "--denovo_families takes a family count from 1 to 8"),
+    (["--denovo", "--denovo_families=9"], "--denovo_families takes a family count from 1 to 8"),
+])
+def test_cli_argument_errors(built, tmp_path, extra, message):
+    out = tmp_path / "out.vcf"
+    r = subprocess.run([pm.BIN_PATH] + BASE + [str(out)] + extra, cwd=EXAMPLE, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 1, r.stdout[-1000:] + r.stderr[-1000:]
+    assert "FATAL ERROR" in r.stdout and message in r.stdout, r.stdout[-1000:]
+    assert not out.exists()
+
+
+def test_cpu_evaluator_refuses_the_flag(cpu_driver, tmp_path):
+    """The host driver on another evaluator (the CPU oracle's) ends with the SiteEvaluator default's message."""
+    out = tmp_path / "out.vcf"
+    r = subprocess.run([cpu_driver] + BASE + [str(out), "--denovo", "--denovo_families", "2"], cwd=EXAMPLE,
+                       capture_output=True, text=True, timeout=60)
+    assert r.returncode == 1 and "--denovo_families needs the GPU engine" in r.stdout, r.stdout[-1000:]
+
+
+def test_abi_and_layout(built):
+    lib = pm.load_library()
+    assert lib.pm_abi_version() == 8
+    assert pm.engine.FAM_LR_DTYPE.itemsize == 16
+    assert [pm.engine.FAM_LR_DTYPE.fields[f][1] for f in ("fam", "pad", "lr")] == [0, 4, 8]
+    for name in ("pm_engine_set_denovo_families", "pm_engine_denovo_families", "pm_engine_denovo_rows"):
+        assert name in pm.engine.EXPORTS and hasattr(C.CDLL(pm.LIB_PATH), name)
+
+
+def test_family_kernel_keeps_founder_and_nuclear_families_in_registers():
+    res = _resources()
+    k = "void k_fam_dnlr<false>(DevArgs, FamLrArgs)"
+    assert k in res and "void k_fam_dnlr<true>(DevArgs, FamLrArgs)" in res, [n for n in res if "fam_dnlr" in n]
+    assert int(res[k]["private_segment_fixed_size"]) == 0, res[k]
