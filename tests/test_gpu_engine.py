@@ -49,6 +49,19 @@ def _run_both(ped, params, sections, batch=4096, chrom_of=lambda lab: pm.PM_CHR_
     return stats
 
 
+# Exact-mode cases where the evaluation counts do NOT all match the oracle's, and why.  The engine adds the
+# families' log10 terms as a fixed tree, the reference serially, so the objective differs in its last bit; where a
+# configuration's objective is flat to that bit (its two alleles have no read support: varllk agrees bit for bit or to
+# an ulp at minimisers as far apart as 0.0001 and 0.57) a tie `fu <= fmin` falls the other way and Brent walks another
+# path to the same likelihood.  compare_results still fails any divergence on a non-flat objective.
+_EXACT_FLAT_SITES = {
+    ("test.ped", ()): "site 78773 (pos 78775): configurations 2 and 3 flat, 22 evaluations against 40",
+    ("test.ped", (("denovo", 1), ("denovo_mut_rate", 1.5e-7))):
+        "sites 1203, 12914, 17514, 56854, 61711: configuration 1 flat (e.g. 22 evaluations against 40)",
+    ("test.ped", (("all_sites", 1),)): "site 78773, as in the first case",
+}
+
+
 @pytest.mark.parametrize("numerics", [pm.NUM_PRODUCT, pm.NUM_EXACT, pm.NUM_POLY])
 @pytest.mark.parametrize("pedfile,kw", [
     ("test.ped", dict()),
@@ -61,7 +74,11 @@ def test_example_sites_match_oracle(built, pedfile, kw, numerics):
     ped = pm.Pedigree(os.path.join(EXAMPLE, "test.dat"), os.path.join(EXAMPLE, pedfile))
     secs = _read_all(ped, EXAMPLE)
     stats = _run_both(ped, pm.Params.defaults(numerics=numerics, **kw), secs)
-    assert sum(s["sites"] for s in stats) == 81016
+    counts = {k: sum(s[k] for s in stats) for k in ("eval_path_mismatch", "flat_divergence")}
+    # exact mode: identical Brent evaluation counts and minimisers wherever no objective is flat to rounding noise
+    if numerics == pm.NUM_EXACT and (pedfile, tuple(sorted(kw.items()))) not in _EXACT_FLAT_SITES:
+        assert counts["eval_path_mismatch"] == 0 and counts["flat_divergence"] == 0, counts
+    assert sum(s["sites"] for s in stats) == 81016, counts
 
 
 def _golden_body(name):

@@ -37,17 +37,24 @@ def test_engine_matches_reference_dump(built, tmp_path, name, numerics):
     if ora:
         ora.begin_section(chrom)
     res, calls = [], []
+    counts = {"oracle eval_path_mismatch": 0, "oracle flat_divergence": 0}
     for s in range(0, len(ref), 128):   # several batches: results must not depend on batching
         e, ec = eng.run(pl[s:s + 128], dm[s:s + 128], ref[s:s + 128])
         if ora:
             o, oc = ora.run(pl[s:s + 128], dm[s:s + 128], ref[s:s + 128])
-            compare_results(e, o, ec, oc, label=f"{name}[{s}] ")
+            st = compare_results(e, o, ec, oc, label=f"{name}[{s}] ")
+            counts["oracle eval_path_mismatch"] += st["eval_path_mismatch"]
+            counts["oracle flat_divergence"] += st["flat_divergence"]
         res.append(e)
     import numpy as np
     res = np.concatenate(res)
-    compare_to_dump(res, golden_dump(name), label=name + " ")
+    st = compare_to_dump(res, golden_dump(name), label=name + " ")
+    counts["dump eval_path_mismatch"] = st["eval_path_mismatch"]
+    counts["dump flat_divergence"] = st["flat_divergence"]
+    if numerics == pm.NUM_EXACT:   # identical Brent evaluation counts (and so minimisers) in exact mode
+        assert not any(counts.values()), (name, counts)
     if ora:
-        assert (eng.counters().as_array() == ora.counters().as_array()).all()
+        assert (eng.counters().as_array() == ora.counters().as_array()).all(), (name, counts)
     eng.close()
 
 
