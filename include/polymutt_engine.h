@@ -269,10 +269,37 @@ int pm_engine_set_denovo_families(pm_engine *eng, int32_t top_k, int32_t want_al
  * want_all).  After PM_EBRENT only the rows before the stuck site are valid, as for the genotype rows. */
 int pm_engine_denovo_families(pm_engine *eng, pm_fam_lr *top, double *sum, double *all);
 
-/* *n_rows = the rows pm_engine_denovo_families writes: the row count the last pm_engine_run / pm_engine_collect
- * returned (after PM_EBRENT: the rows before the stuck site), or after pm_engine_run_device + pm_engine_sync the
- * batch's written records (the results with call_row >= 0). */
+/* *n_rows = the rows pm_engine_denovo_families and pm_engine_denovo_carriers write (0 with both features off): the
+ * row count the last pm_engine_run / pm_engine_collect returned (after PM_EBRENT: the rows before the stuck site), or
+ * after pm_engine_run_device + pm_engine_sync the batch's written records (the results with call_row >= 0). */
 int pm_engine_denovo_rows(pm_engine *eng, int32_t *n_rows);
+
+/* Per-person de novo posteriors (--denovo engines, not vcf_mode; additive to ABI 8: callers detect the feature by
+ * these symbols).  For every written record (emit == 1) and every non-founder c with father fa and mother mo, in the
+ * alleles and frequency of pm_engine_denovo_families' numerator (maxidx >= 1: allele1, allele2 at varfreq[maxidx];
+ * maxidx == 0: ref, ref == 4 ? 3 : ref + 1 at 1.0), with L_f the de novo-model likelihood of c's family (a sum over
+ * the joint genotypes of its members) and J_c(a, b, S) the same sum restricted to G_fa = a, G_mo = b, G_c in S:
+ *   pp    = Sum_{a,b} J_c(a, b, NonMend(a, b)) / L_f, NonMend(a, b) = the genotypes that cannot take one allele from a
+ *           and one from b (the autosomal rule on every chromosome class, as the de novo model's transmission);
+ *   event = (fa_g, mo_g) maximising J_c(a, b, NonMend(a, b)) (ties: the first pair in (a, b) order), then kid_g
+ *           maximising J_c(fa_g, mo_g, {g}) over NonMend(fa_g, mo_g) (ties: the lowest g); (-1, -1, -1) when every
+ *           term is 0.
+ * Genotypes are indices 0..9 in GLF order (AA, AC, AG, AT, CC, CG, CT, GG, GT, TT).  One extra kernel per batch
+ * (k_person_dn) over the written rows only; results are deterministic (fixed reduction trees, no atomics). */
+typedef struct { int32_t person; int8_t fa_g, mo_g, kid_g, pad; double pp; } pm_person_dn;   /* 16 bytes; person = index in pm_pedigree order */
+
+/* top_k = 0 switches the feature off (the default: nothing is allocated or launched, every output is bit-identical);
+ * 1..8 keeps, per written record, the top_k non-founders ranked by pp descending, ties by lower person index.
+ * want_all != 0 also keeps the full [max_batch][n_person] matrix on the device (PM_EINVAL above 1 GiB).
+ * PM_EINVAL: top_k out of range, an engine without denovo, a vcf_mode engine, or a submitted batch not yet collected.
+ * Independent of pm_engine_set_denovo_families: either, both or neither may be on. */
+int pm_engine_set_denovo_carriers(pm_engine *eng, int32_t top_k, int32_t want_all);
+
+/* The rows of the last finished batch, indexed by pm_site_result.call_row (pm_engine_denovo_rows tells how many, with
+ * either feature on): top[n_rows][top_k] (entries past the non-founder count are {-1, -1, -1, -1, 0, 0.0}) and
+ * all[n_rows][n_person] (person = p; founders have genotypes -1 and pp 0; may be NULL, PM_EINVAL when asked for
+ * without want_all).  After PM_EBRENT only the rows before the stuck site are valid. */
+int pm_engine_denovo_carriers(pm_engine *eng, pm_person_dn *top, pm_person_dn *all);
 
 /* Page-locked host memory for pm_engine_submit's inputs and the result rows (H2D/D2H at full PCIe rate). */
 int pm_host_alloc(uint64_t bytes, void **h_ptr);

@@ -109,9 +109,17 @@ struct pm_engine {
   int* d_row_blk = nullptr;   // k_rows_count: written records per 1024-site block
   // per-family de novo evidence (pm_engine_set_denovo_families): off (top_k 0) = no buffer, no launch
   int fam_top_k = 0, fam_grid = 0;
-  int last_rows = 0;          // written rows of the last finished batch (pm_engine_denovo_families)
+  int last_rows = 0;          // written rows of the last finished batch (pm_engine_denovo_families / _carriers)
   pm_fam_lr* d_fam_top = nullptr;                                      // [max_batch][top_k]
   double *d_fam_sum = nullptr, *d_fam_all = nullptr, *d_fam_line = nullptr;   // [max_batch], [max_batch][n_fam] | [fam_grid][n_fam]
+  // per-person de novo posteriors (pm_engine_set_denovo_carriers): off (top_k 0) = no buffer, no launch
+  int pdn_top_k = 0, pdn_grid = 0, pdn_n_nuc = 0, pdn_n_es = 0;
+  pm_person_dn *d_pdn_top = nullptr, *d_pdn_all = nullptr, *d_pdn_line = nullptr;   // [max_batch][top_k], [max_batch][n_person] | [pdn_grid][n_person]
+  int2* d_pdn_kids = nullptr;       // the non-founders {family, member}: nuclear families' in fam_perm order, then extended families'
+  int8_t* d_pdn_is_kid = nullptr;   // [n_person]
+  double* d_pdn_jbuf = nullptr;     // [pdn_grid][pdn_n_es * 111] clamped-peel values of k_person_dn<true>
+  std::vector<int> fam_kind_h, fam_perm_h;
+  std::vector<int32_t> fa_h, mo_h;  // family-local parent indices (-1: none)
   unsigned long long* d_counters = nullptr;
   double M_h[100];
   // stats
@@ -319,7 +327,8 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_fam_start, E->d_fam_kind, E->d_fa, E->d_mo, E->d_sex, E->d_units, E->d_lktab, E->d_M, E->d_syn,
                   E->d_pl, E->d_stage, E->d_ref, E->d_dm, E->d_res, E->d_calls, E->d_raw, E->d_minv, E->d_mono, E->d_evals,
                   E->d_items[0], E->d_items[1], E->d_items[2], E->d_counts, E->d_eval_total, E->d_row_site,
-                  E->d_counters, E->d_row_blk, E->d_qctr, E->d_fam_top, E->d_fam_sum, E->d_fam_all, E->d_fam_line};
+                  E->d_counters, E->d_row_blk, E->d_qctr, E->d_fam_top, E->d_fam_sum, E->d_fam_all, E->d_fam_line,
+                  E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf};
   for (void* b : bufs) if (b) hipFree(b);
   for (auto& pl : E->d_jit_slots)
     for (int* b : pl) if (b) hipFree(b);
@@ -523,6 +532,8 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
         fa[j] = ped->father[j] < 0 ? -1 : ped->father[j] - ped->fam_start[f];
         mo[j] = ped->mother[j] < 0 ? -1 : ped->mother[j] - ped->fam_start[f];
       }
+  E->fa_h = fa; E->mo_h = mo;
+  E->fam_kind_h.assign(ped->fam_kind, ped->fam_kind + ped->n_fam);
   DALLOC(E->d_fam_start, ped->n_fam + 1);
   DALLOC(E->d_fam_kind, ped->n_fam);
   DALLOC(E->d_fa, ped->n_person);
@@ -548,6 +559,7 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
       const int na = ped->fam_start[a + 1] - ped->fam_start[a], nb = ped->fam_start[b + 1] - ped->fam_start[b];
       return ped->fam_kind[a] != ped->fam_kind[b] ? ped->fam_kind[a] < ped->fam_kind[b] : na < nb;
     });
+    E->fam_perm_h = perm;
     DALLOC(E->d_fam_perm, ped->n_fam);
     HIP_TRY(hipMemcpy(E->d_fam_perm, perm.data(), sizeof(int) * ped->n_fam, hipMemcpyHostToDevice));
   }
@@ -1344,6 +1356,14 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
     hipLaunchKernelGGL(E->n_ext > 0 ? k_fam_dnlr<true> : k_fam_dnlr<false>, dim3(grid), dim3(256), 0, E->stream, A, F);
     HIP_TRY(hipGetLastError());
   }
+  if (E->pdn_top_k > 0) {   // per-person de novo posteriors of the written rows (the same workspace, after k_fam_dnlr on the stream)
+    PersonDnArgs P;
+    P.top_k = E->pdn_top_k; P.top = E->d_pdn_top; P.all = E->d_pdn_all; P.line = E->d_pdn_line; P.kids = E->d_pdn_kids;
+    P.n_nuc = E->pdn_n_nuc; P.n_es = E->pdn_n_es; P.is_kid = E->d_pdn_is_kid; P.jbuf = E->d_pdn_jbuf;
+    const int grid = std::max(1, std::min(E->pdn_grid, n));
+    hipLaunchKernelGGL(E->pdn_n_es > 0 ? k_person_dn<true> : k_person_dn<false>, dim3(grid), dim3(256), 0, E->stream, A, P);
+    HIP_TRY(hipGetLastError());
+  }
   return PM_OK;
 }
 
@@ -1432,7 +1452,77 @@ int pm_engine_set_denovo_families(pm_engine* E, int32_t top_k, int32_t want_all)
 
 int pm_engine_denovo_rows(pm_engine* E, int32_t* n_rows) {
   if (!E || !n_rows) { pm_set_last_error("pm_engine_denovo_rows: invalid arguments"); return PM_EINVAL; }
-  *n_rows = E->fam_top_k > 0 ? E->last_rows : 0;
+  *n_rows = (E->fam_top_k > 0 || E->pdn_top_k > 0) ? E->last_rows : 0;
+  return PM_OK;
+}
+
+int pm_engine_set_denovo_carriers(pm_engine* E, int32_t top_k, int32_t want_all) {
+  if (!E || top_k < 0 || top_k > 8) { pm_set_last_error("pm_engine_set_denovo_carriers: top_k must be 0 (off) or 1..8"); return PM_EINVAL; }
+  if (E->vcf) { pm_set_last_error("pm_engine_set_denovo_carriers: not available on a vcf_mode engine"); return PM_EINVAL; }
+  if (!E->par.denovo) { pm_set_last_error("pm_engine_set_denovo_carriers: the engine was created without denovo"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_denovo_carriers: a submitted batch has not been collected"); return PM_EINVAL; }
+  const size_t nb = (size_t)E->max_batch, np = (size_t)E->n_person;
+  if (top_k > 0 && want_all && nb * np * sizeof(pm_person_dn) > ((size_t)1 << 30)) {
+    char b[256];
+    snprintf(b, sizeof(b), "pm_engine_set_denovo_carriers: want_all needs max_batch x n_person x 16 = %zu bytes on the device (limit 1 GiB)",
+             nb * np * sizeof(pm_person_dn));
+    pm_set_last_error(b);
+    return PM_EINVAL;
+  }
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  E->pdn_top_k = 0;
+  E->last_rows = 0;   // (either setter forgets the last batch's rows: the buffers it fills are new)
+  void** bufs[] = {(void**)&E->d_pdn_top, (void**)&E->d_pdn_all, (void**)&E->d_pdn_line, (void**)&E->d_pdn_kids, (void**)&E->d_pdn_is_kid,
+                   (void**)&E->d_pdn_jbuf};
+  for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+  if (top_k == 0) return PM_OK;
+  // the work list: every person with both parents in a nuclear or an extended family
+  std::vector<int2> kids, kids_es;
+  std::vector<int8_t> is_kid(np, 0);
+  for (int f : E->fam_perm_h) {
+    const int kind = E->fam_kind_h[f], p0 = E->fam_start_h[f], n = E->fam_start_h[f + 1] - p0;
+    if (kind == PM_FAM_FOUNDERS) continue;
+    for (int j = 0; j < n; j++) {
+      const int fa = E->fa_h[p0 + j], mo = E->mo_h[p0 + j];
+      if (fa < 0 || mo < 0 || fa >= n || mo >= n) continue;
+      if (kind == PM_FAM_NUCLEAR && (j < 2 || fa > 1 || mo > 1 || fa == mo)) continue;   // (a nuclear family is father, mother, kids)
+      (kind == PM_FAM_NUCLEAR ? kids : kids_es).push_back(make_int2(f, j));
+      is_kid[p0 + j] = 1;
+    }
+  }
+  E->pdn_n_nuc = (int)kids.size();
+  E->pdn_n_es = (int)kids_es.size();
+  kids.insert(kids.end(), kids_es.begin(), kids_es.end());
+  // one block per row at a time; the extended families' term buffer caps the grid at 256 MiB
+  E->pdn_grid = E->grid_post;
+  const size_t per_block = (size_t)E->pdn_n_es * 111 * sizeof(double);
+  if (per_block) E->pdn_grid = (int)std::max<size_t>(1, std::min<size_t>(E->pdn_grid, ((size_t)1 << 28) / per_block));
+  int rc;
+  if ((rc = dalloc(&E->d_pdn_top, nb * top_k)) || (rc = dalloc(&E->d_pdn_kids, std::max<size_t>(1, kids.size()))) ||
+      (rc = dalloc(&E->d_pdn_is_kid, np)))
+    return rc;
+  if (want_all) rc = dalloc(&E->d_pdn_all, nb * np);
+  else rc = dalloc(&E->d_pdn_line, (size_t)E->pdn_grid * np);
+  if (rc) return rc;
+  if (per_block && (rc = dalloc(&E->d_pdn_jbuf, (size_t)E->pdn_grid * E->pdn_n_es * 111))) return rc;
+  if (!kids.empty()) HIP_TRY(hipMemcpy(E->d_pdn_kids, kids.data(), sizeof(int2) * kids.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(E->d_pdn_is_kid, is_kid.data(), np, hipMemcpyHostToDevice));
+  E->pdn_top_k = top_k;
+  return PM_OK;
+}
+
+int pm_engine_denovo_carriers(pm_engine* E, pm_person_dn* top, pm_person_dn* all) {
+  if (!E || !top) { pm_set_last_error("pm_engine_denovo_carriers: invalid arguments"); return PM_EINVAL; }
+  if (E->pdn_top_k <= 0) { pm_set_last_error("pm_engine_denovo_carriers: the feature is off (pm_engine_set_denovo_carriers)"); return PM_EINVAL; }
+  if (all && !E->d_pdn_all) { pm_set_last_error("pm_engine_denovo_carriers: the full matrix needs want_all"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_denovo_carriers: a submitted batch has not been collected"); return PM_EINVAL; }
+  const size_t rows = (size_t)E->last_rows;
+  if (rows == 0) return PM_OK;
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  HIP_TRY(hipMemcpy(top, E->d_pdn_top, sizeof(pm_person_dn) * rows * E->pdn_top_k, hipMemcpyDeviceToHost));
+  if (all) HIP_TRY(hipMemcpy(all, E->d_pdn_all, sizeof(pm_person_dn) * rows * E->n_person, hipMemcpyDeviceToHost));
   return PM_OK;
 }
 

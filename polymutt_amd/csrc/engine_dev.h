@@ -383,9 +383,12 @@ __device__ __forceinline__ double d_tba(int i, int j, int k, int chrom, int chil
   return t;
 }
 
-template <int NS>
+// CL (10-state only): three more persons c0, c1, c2 (family-local indices) are clamped to the genotype sets m0, m1, m2
+// (bit g = genotype g allowed), the zp / zg clamp generalised to masks (k_person_dn); without CL nothing is added.
+template <int NS, bool CL = false>
 __device__ __forceinline__ double d_es_lk(const DevArgs& A, int f, const uint8_t* pl, const double* lk, int g11, int g12, int g22, int chrom,
-                          double freq, int zp, int zg, double* ws, size_t st) {
+                          double freq, int zp, int zg, double* ws, size_t st, int c0 = -1, int m0 = 0, int c1 = -1, int m1 = 0,
+                          int c2 = -1, int m2 = 0) {
   const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0, nf = A.fam_founders[f];
   const bool X = chrom == PM_CHR_X, Y = chrom == PM_CHR_Y, MT = chrom == PM_CHR_MT;
   const int gidx[3] = {g11, g12, g22};
@@ -424,7 +427,9 @@ __device__ __forceinline__ double d_es_lk(const DevArgs& A, int f, const uint8_t
       }
 #pragma unroll
       for (int j = 0; j < 10; j++) {
-        const double pen = (zp == i && j != zg) ? 0.0 : lk[R[j * np]];
+        double pen = (zp == i && j != zg) ? 0.0 : lk[R[j * np]];
+        if (CL)
+          if ((i == c0 && !((m0 >> j) & 1)) || (i == c1 && !((m1 >> j) & 1)) || (i == c2 && !((m2 >> j) & 1))) pen = 0.0;
         PP(i, j) = fo ? pr[j] * pen : pen;
       }
     }
@@ -3462,6 +3467,257 @@ __global__ void __launch_bounds__(256) k_fam_dnlr(DevArgs A, FamLrArgs F) {
       if (bf == INT_MAX) { prev_lr = -INFINITY; prev_f = INT_MAX; }   // exhausted: every later round is empty too
       else { prev_lr = bl; prev_f = bf; }
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_person_dn: per-person de novo posteriors of the written rows (pm_engine_denovo_carriers; no reference counterpart).
+// In k_fam_dnlr's numerator model (alleles, frequency, prior mode, member sex 0) the family likelihood L_f is a sum
+// over the joint genotypes of its members; for a non-founder c with father fa and mother mo
+//   pp_c = Sum_{a,b} J_c(a, b, NonMend(a, b)) / L_f,   J_c(a, b, S) = that sum restricted to G_fa = a, G_mo = b, G_c in S,
+// and the event is the (a, b) of the largest term, then the g in NonMend(a, b) of the largest J_c(a, b, {g}).
+// One block per written row at a time.
+//  * Nuclear families: one lane per child, the children in fam_perm order (P.kids).  The nuclear closed form factorises
+//    per parental configuration k into prior x parents x every kid's factor, so the lane forms the product without its
+//    own factor (the hoist of the family around c), then splits c's factor -- the mutation-matrix rows D11 / D12 / D22
+//    of hoist_nuc, term by term in g -- into the Mendelian genotypes of configuration k and the rest.  Registers only.
+//  * Extended families (ES): stage A, one peel per (child, a, b) with father and mother clamped to a and b and the child
+//    to NonMend(a, b) (d_es_lk<10, true>, items across the block's threads, pairs outside a founder parent's three
+//    genotypes skipped: their prior is 0), values to the block's line of P.jbuf; stage B, per (child, slot) the
+//    unclamped L_f (slot 10) and the best pair's peel with the child clamped to g (slots 0..9); stage C, one thread
+//    per child adds the 100 terms in (a, b) order and writes the entry.  Barriers between the stages.
+// The ranking is k_fam_dnlr's: top_k rounds of a fixed-tree block reduction, so the same input gives the same bits.
+struct PersonDnArgs {
+  int top_k;                // 1..8
+  pm_person_dn* top;        // [rows][top_k]
+  pm_person_dn* all;        // [rows][n_person], or null
+  pm_person_dn* line;       // [gridDim.x][n_person] when all is null
+  const int2* kids;         // the non-founders {family, member}: n_nuc of nuclear families in fam_perm order, then n_es of extended ones
+  int n_nuc, n_es;
+  const int8_t* is_kid;     // [n_person] 1 = listed in kids
+  double* jbuf;             // ES: [gridDim.x][n_es * 111]
+};
+
+// genotype index (GLF order) -> its alleles 1..4, x <= y (the inverse of d_gi)
+__device__ __forceinline__ void d_g_alleles(int g, int* x, int* y) {
+  const int a = g < 4 ? 1 : g < 7 ? 2 : g < 9 ? 3 : 4, base = g < 4 ? 0 : g < 7 ? 4 : g < 9 ? 7 : 9;
+  *x = a; *y = a + (g - base);
+}
+// bit g = genotype g takes one allele from a and one from b
+__device__ __forceinline__ int d_mendel_mask(int a, int b) {
+  int a1, a2, b1, b2;
+  d_g_alleles(a, &a1, &a2);
+  d_g_alleles(b, &b1, &b2);
+  return (1 << d_gi(a1, b1)) | (1 << d_gi(a1, b2)) | (1 << d_gi(a2, b1)) | (1 << d_gi(a2, b2));
+}
+// nuclear configuration k = 3 * father + mother over (11, 12, 22): its Mendelian kid genotypes, bit 0 = 11, 1 = 12, 2 = 22
+__device__ __forceinline__ int d_mend3(int k) {
+  return (int)((((1ull | 3ull << 3 | 2ull << 6 | 3ull << 9 | 7ull << 12 | 6ull << 15 | 2ull << 18 | 6ull << 21 | 4ull << 24)) >> (3 * k)) & 7);
+}
+
+template <bool ES>
+__global__ void __launch_bounds__(256) k_person_dn(DevArgs A, PersonDnArgs P) {
+  __shared__ double s_lk[256];
+  __shared__ double s_M[100];
+  __shared__ double s_red[2][4];
+  __shared__ int s_redf[2][4];
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lk[i] = A.lktab[i];
+  for (int i = threadIdx.x; i < 100; i += blockDim.x) s_M[i] = A.M[i];
+  __syncthreads();
+  const int rows = A.counts[3], np = A.n_person, nk = P.n_nuc + P.n_es;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const size_t ws_stride = (size_t)gridDim.x * blockDim.x;
+  double* wsl = ES ? A.ws + (size_t)blockIdx.x * blockDim.x + threadIdx.x : nullptr;
+  double* jb = ES ? P.jbuf + (size_t)blockIdx.x * P.n_es * 111 : nullptr;
+  (void)wsl; (void)ws_stride; (void)jb;
+  int par = 0;
+  for (int row = blockIdx.x; row < rows; row += gridDim.x) {   // (block-uniform: every thread reaches the barriers)
+    const int site = A.row_site[row];
+    const pm_site_result* R = A.res + site;
+    const uint8_t* pl = A.pl + (size_t)site * np * 10;
+    const int mx = R->maxidx, r = A.ref[site];
+    const bool mono = mx <= 0;
+    ItemCtx I;
+    if (mono) cfg_alleles(0, r, &I.a1, &I.a2);
+    else { I.a1 = R->allele1; I.a2 = R->allele2; }
+    I.g11 = d_gi(I.a1, I.a1); I.g12 = d_gi(I.a1, I.a2); I.g22 = d_gi(I.a2, I.a2);
+    I.sex = 0; I.chrom = A.chrom; I.denovo = 1;
+    const double x = mono ? 1.0 : R->varfreq[mx];
+    double pp9[9];
+    d_parent_prior(A.n_fam_gt1 ? PR_AUTO : PR_DN_SINGLE, x, pp9);
+    pm_person_dn* line = P.all ? P.all + (size_t)row * np : P.line + (size_t)blockIdx.x * np;
+    for (int p = threadIdx.x; p < np; p += blockDim.x)   // founders (and anyone without both parents): no value
+      if (!P.is_kid[p]) {
+        pm_person_dn o;
+        o.person = p; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
+        line[p] = o;
+      }
+    // ---- nuclear families: one child per lane
+    for (int ci = threadIdx.x; ci < P.n_nuc; ci += blockDim.x) {
+      const int2 kd = P.kids[ci];
+      const int p0 = A.fam_start[kd.x], n = A.fam_start[kd.x + 1] - p0, jc = kd.y;
+      const bool sw = A.fa_local[p0 + jc] == 1;   // (hoist_nuc's first parent is person p0: the father unless the family lists the mother first)
+      const double lF[3] = {s_lk[PLB(pl, np, p0, I.g11)], s_lk[PLB(pl, np, p0, I.g12)], s_lk[PLB(pl, np, p0, I.g22)]};
+      const double lM[3] = {s_lk[PLB(pl, np, p0 + 1, I.g11)], s_lk[PLB(pl, np, p0 + 1, I.g12)], s_lk[PLB(pl, np, p0 + 1, I.g22)]};
+      double w[9];   // the family around c: every other kid's factor, the parents, the prior
+#pragma unroll
+      for (int k = 0; k < 9; k++) w[k] = 1.0;
+      for (int j = 2; j < n; j++) {
+        if (j == jc) continue;
+        const uint8_t* K = pl + p0 + j;
+        double D11 = 0.0, D12 = 0.0, D22 = 0.0;
+#pragma unroll
+        for (int g = 0; g < 10; g++) {
+          const double pg = s_lk[K[(size_t)g * np]];
+          D11 += s_M[I.g11 * 10 + g] * pg;
+          D12 += s_M[I.g12 * 10 + g] * pg;
+          D22 += s_M[I.g22 * 10 + g] * pg;
+        }
+#pragma unroll
+        for (int k = 0; k < 9; k++) w[k] *= d_one_kid_dn(k, D11, D12, D22);
+      }
+#pragma unroll
+      for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) w[3 * a + b] = (w[3 * a + b] * (lF[a] * lM[b])) * pp9[3 * a + b];
+      // c's own factor, split by genotype: e[row][s] = the term of g = (g11, g12, g22)[s], o[row] = the other seven
+      const uint8_t* K = pl + p0 + jc;
+      double o3[3] = {0.0, 0.0, 0.0}, e[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+      for (int g = 0; g < 10; g++) {
+        const double pg = s_lk[K[(size_t)g * np]];
+        const double t0 = s_M[I.g11 * 10 + g] * pg, t1 = s_M[I.g12 * 10 + g] * pg, t2 = s_M[I.g22 * 10 + g] * pg;
+        if (g == I.g11) { e[0][0] = t0; e[1][0] = t1; e[2][0] = t2; }
+        else if (g == I.g12) { e[0][1] = t0; e[1][1] = t1; e[2][1] = t2; }
+        else if (g == I.g22) { e[0][2] = t0; e[1][2] = t1; e[2][2] = t2; }
+        else { o3[0] += t0; o3[1] += t1; o3[2] += t2; }
+      }
+      const int gidx[3] = {I.g11, I.g12, I.g22};
+      double num = 0.0, den = 0.0, bj = 0.0, bw = 0.0;
+      int bk = -1, bfa = -1, bmo = -1;
+#pragma unroll
+      for (int k = 0; k < 9; k++) {
+        const int md = d_mend3(k);
+        double nm[3], me[3];
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+          nm[q] = o3[q]; me[q] = 0.0;
+#pragma unroll
+          for (int s = 0; s < 3; s++) {
+            if ((md >> s) & 1) me[q] += e[q][s];
+            else nm[q] += e[q][s];
+          }
+        }
+        const double fn = d_one_kid_dn(k, nm[0], nm[1], nm[2]), fm = d_one_kid_dn(k, me[0], me[1], me[2]);
+        const double Jn = w[k] * fn;
+        num += Jn;
+        den += w[k] * (fn + fm);   // (term by term >= Jn: num <= den, pp <= 1)
+        const int ga = gidx[k / 3], gb = gidx[k % 3];
+        const int fg = sw ? gb : ga, mg = sw ? ga : gb;
+        if (Jn > bj || (Jn == bj && bk >= 0 && (fg < bfa || (fg == bfa && mg < bmo)))) { bj = Jn; bw = w[k]; bk = k; bfa = fg; bmo = mg; }
+      }
+      int bg = -1;
+      if (bk >= 0) {   // the largest single-genotype term of the best configuration
+        const int md = d_mend3(bk);
+        double bv = 0.0;
+        for (int g = 0; g < 10; g++) {
+          if ((g == I.g11 && (md & 1)) || (g == I.g12 && (md & 2)) || (g == I.g22 && (md & 4))) continue;
+          const double pg = s_lk[K[(size_t)g * np]];
+          const double v = bw * d_one_kid_dn(bk, s_M[I.g11 * 10 + g] * pg, s_M[I.g12 * 10 + g] * pg, s_M[I.g22 * 10 + g] * pg);
+          if (v > bv) { bv = v; bg = g; }
+        }
+        if (bg < 0) { bfa = -1; bmo = -1; }
+      }
+      pm_person_dn o;
+      o.person = p0 + jc; o.fa_g = (int8_t)bfa; o.mo_g = (int8_t)bmo; o.kid_g = (int8_t)bg; o.pad = 0;
+      o.pp = den > 0.0 ? num / den : 0.0;
+      line[p0 + jc] = o;
+    }
+    // ---- extended families: clamped peels
+    if constexpr (ES) {
+      for (int it = threadIdx.x; it < P.n_es * 100; it += blockDim.x) {   // stage A
+        const int ci = it / 100, a = (it / 10) % 10, b = it % 10;
+        const int2 kd = P.kids[P.n_nuc + ci];
+        const int p0 = A.fam_start[kd.x], jc = kd.y, fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
+        const bool a3 = a == I.g11 || a == I.g12 || a == I.g22, b3 = b == I.g11 || b == I.g12 || b == I.g22;
+        double J = 0.0;
+        if ((a3 || !A.is_founder[p0 + fa]) && (b3 || !A.is_founder[p0 + mo]))
+          J = d_es_lk<10, true>(A, kd.x, pl, s_lk, I.g11, I.g12, I.g22, A.chrom, x, -1, -1, wsl, ws_stride, fa, 1 << a, mo, 1 << b, jc,
+                                0x3FF & ~d_mendel_mask(a, b));
+        jb[it] = J;
+      }
+      __syncthreads();
+      double* jb2 = jb + (size_t)P.n_es * 100;
+      for (int it = threadIdx.x; it < P.n_es * 11; it += blockDim.x) {   // stage B
+        const int ci = it / 11, slot = it % 11;
+        const int2 kd = P.kids[P.n_nuc + ci];
+        const int p0 = A.fam_start[kd.x], jc = kd.y, fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
+        double v = -1.0;
+        if (slot == 10) v = d_es_lk<10>(A, kd.x, pl, s_lk, I.g11, I.g12, I.g22, A.chrom, x, -1, -1, wsl, ws_stride);
+        else {
+          double bj = 0.0;
+          int bi = -1;
+          for (int q = 0; q < 100; q++) { const double J = jb[ci * 100 + q]; if (J > bj) { bj = J; bi = q; } }
+          if (bi >= 0 && !((d_mendel_mask(bi / 10, bi % 10) >> slot) & 1))
+            v = d_es_lk<10, true>(A, kd.x, pl, s_lk, I.g11, I.g12, I.g22, A.chrom, x, -1, -1, wsl, ws_stride, fa, 1 << (bi / 10), mo,
+                                  1 << (bi % 10), jc, 1 << slot);
+        }
+        jb2[it] = v;
+      }
+      __syncthreads();
+      for (int ci = threadIdx.x; ci < P.n_es; ci += blockDim.x) {   // stage C
+        const int2 kd = P.kids[P.n_nuc + ci];
+        const int p = A.fam_start[kd.x] + kd.y;
+        double num = 0.0, bj = 0.0;
+        int bi = -1;
+        for (int q = 0; q < 100; q++) { const double J = jb[ci * 100 + q]; num += J; if (J > bj) { bj = J; bi = q; } }
+        const double L = jb2[ci * 11 + 10];
+        double bv = 0.0;
+        int bg = -1;
+        for (int g = 0; g < 10; g++) { const double v = jb2[ci * 11 + g]; if (v > bv) { bv = v; bg = g; } }
+        pm_person_dn o;
+        o.person = p; o.pad = 0;
+        o.fa_g = (int8_t)(bg < 0 ? -1 : bi / 10); o.mo_g = (int8_t)(bg < 0 ? -1 : bi % 10); o.kid_g = (int8_t)bg;
+        o.pp = L > 0.0 ? fmin(num / L, 1.0) : 0.0;   // (L_f and the terms come from separate peels: rounding may pass 1)
+        line[p] = o;
+      }
+    }
+    __syncthreads();   // the row's entries are visible to the block: the ranking reads what other threads wrote
+    double prev_pp = 0.0;
+    int prev_p = -1;
+    for (int k = 0; k < P.top_k; k++) {   // round k takes the best entry that comes after round k - 1's in the order
+      double bl = 0.0;
+      int bf = INT_MAX;
+      for (int i = threadIdx.x; i < nk; i += blockDim.x) {
+        const int2 kd = P.kids[i];
+        const int p = A.fam_start[kd.x] + kd.y;
+        const double d = line[p].pp;
+        const bool after = k == 0 ? d == d : (d < prev_pp || (d == prev_pp && p > prev_p));
+        if (after && fam_lr_before(d, p, bl, bf)) { bl = d; bf = p; }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const double ol = __shfl_xor(bl, o, 64);
+        const int of = __shfl_xor(bf, o, 64);
+        if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
+      }
+      if (lane == 0) { s_red[par][wv] = bl; s_redf[par][wv] = bf; }
+      __syncthreads();
+      bl = s_red[par][0]; bf = s_redf[par][0];
+#pragma unroll
+      for (int w = 1; w < 4; w++)
+        if (fam_lr_before(s_red[par][w], s_redf[par][w], bl, bf)) { bl = s_red[par][w]; bf = s_redf[par][w]; }
+      par ^= 1;
+      if (threadIdx.x == 0) {
+        pm_person_dn o;
+        o.person = -1; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
+        if (bf != INT_MAX) o = line[bf];
+        P.top[(size_t)row * P.top_k + k] = o;
+      }
+      if (bf == INT_MAX) { prev_pp = -INFINITY; prev_p = INT_MAX; }   // exhausted: every later round is empty too
+      else { prev_pp = bl; prev_p = bf; }
+    }
+    __syncthreads();   // (the next row rewrites the block's line and jbuf)
   }
 }
 

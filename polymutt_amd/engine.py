@@ -101,6 +101,8 @@ assert SITE_DTYPE.itemsize == C.sizeof(SiteResult) == 240, SITE_DTYPE.itemsize
 assert CALL_DTYPE.itemsize == C.sizeof(GenoCall) == 16
 FAM_LR_DTYPE = np.dtype([("fam", "<i4"), ("pad", "<i4"), ("lr", "<f8")])   # pm_fam_lr
 assert FAM_LR_DTYPE.itemsize == 16
+PERSON_DN_DTYPE = np.dtype([("person", "<i4"), ("fa_g", "i1"), ("mo_g", "i1"), ("kid_g", "i1"), ("pad", "i1"), ("pp", "<f8")])   # pm_person_dn
+assert PERSON_DN_DTYPE.itemsize == 16
 
 _lib = None
 
@@ -121,6 +123,8 @@ EXPORTS = {
     "pm_engine_set_denovo_families": (i32, [C.c_void_p, i32, i32]),
     "pm_engine_denovo_families": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_engine_denovo_rows": (i32, [C.c_void_p, P(i32)]),
+    "pm_engine_set_denovo_carriers": (i32, [C.c_void_p, i32, i32]),
+    "pm_engine_denovo_carriers": (i32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_host_alloc": (i32, [u64, P(C.c_void_p)]),
     "pm_host_free": (i32, [C.c_void_p]),
     "pm_engine_to_planar": (i32, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
@@ -261,6 +265,7 @@ class Engine:
         self.h = h
         self.n_fam = ped_struct.n_fam
         self._fam_k, self._fam_all = 0, False
+        self._pdn_k, self._pdn_all = 0, False
 
     def begin_section(self, chrom=PM_CHR_AUTO):
         self._check(self.lib.pm_engine_begin_section(self.h, chrom))
@@ -376,6 +381,26 @@ class Engine:
         full = np.zeros((rows, self.n_fam), dtype=np.float64) if self._fam_all else None
         self._check(self.lib.pm_engine_denovo_families(self.h, _ptr(top), _ptr(tot), None if full is None else _ptr(full)))
         return top, tot, full
+
+    def set_denovo_carriers(self, top_k, want_all=False):
+        """pm_engine_set_denovo_carriers: keep, per written de novo record, the top_k (1..8; 0 = off) non-founders ranked by
+        their posterior probability of carrying a de novo mutation, each with its most likely event (father, mother and
+        child genotype, indices 0..9 in GLF order), and with want_all the whole [rows, n_person] matrix."""
+        self._check(self.lib.pm_engine_set_denovo_carriers(self.h, int(top_k), 1 if want_all else 0))
+        self._pdn_k, self._pdn_all = int(top_k), bool(want_all) and top_k > 0
+
+    def denovo_carriers(self):
+        """pm_engine_denovo_carriers for the last finished batch (run(), collect(), or run_device() + sync()):
+        (top[rows, k], all[rows, n_person] or None) of PERSON_DN_DTYPE, rows indexed by call_row."""
+        if self._pdn_k <= 0:
+            raise RuntimeError("denovo_carriers: the feature is off (set_denovo_carriers)")
+        n = i32(0)
+        self._check(self.lib.pm_engine_denovo_rows(self.h, C.byref(n)))
+        rows = n.value
+        top = np.zeros((rows, self._pdn_k), dtype=PERSON_DN_DTYPE)
+        full = np.zeros((rows, self.n_person), dtype=PERSON_DN_DTYPE) if self._pdn_all else None
+        self._check(self.lib.pm_engine_denovo_carriers(self.h, _ptr(top), None if full is None else _ptr(full)))
+        return top, full
 
     def stuck_site(self):
         """pm_engine_stuck_site: the first site of the last finished batch whose Brent hit ITMAX (-1: none)."""

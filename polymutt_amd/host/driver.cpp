@@ -48,7 +48,7 @@ Options parse_command_line(int argc, char** argv) {
       // engine options (not in the reference)
       {"gpu", 'i', &o.device}, {"batch", 'i', &o.batch}, {"io_threads", 'i', &o.io_threads}, {"engines", 'i', &o.engines},
       {"in_blocks", 's', &o.blocksIn}, {"glf2blocks", 's', &o.blocksOut}, {"block_sites", 'i', &o.blockSites}, {"exact_log10", 'b', &o.exact_log10}, {"numerics", 's', &o.numerics},
-      {"denovo_families", 'i', &o.denovo_families},
+      {"denovo_families", 'i', &o.denovo_families}, {"denovo_carriers", 'i', &o.denovo_carriers},
   };
   auto assign = [](Flag& f, const char* v) {
     switch (f.kind) {
@@ -69,6 +69,7 @@ Options parse_command_line(int argc, char** argv) {
         if (name != f.name) continue;
         found = true;
         if (f.ptr == &o.denovo_families) o.denovo_families_given = true;
+        if (f.ptr == &o.denovo_carriers) o.denovo_carriers_given = true;
         if (f.kind == 'b') { *(bool*)f.ptr = true; break; }
         if (!hasEq) {
           if (a + 1 >= argc) throw FatalError(std::string("Missing value for option --") + name + "\n");
@@ -96,6 +97,11 @@ Options parse_command_line(int argc, char** argv) {
     if (!o.denovo) throw FatalError("--denovo_families needs --denovo\n");
     if (!o.vcfInFile.empty()) throw FatalError("--denovo_families is not available with --in_vcf\n");
     if (o.denovo_families < 1 || o.denovo_families > 8) throw FatalError("--denovo_families takes a family count from 1 to 8\n");
+  }
+  if (o.denovo_carriers_given) {
+    if (!o.denovo) throw FatalError("--denovo_carriers needs --denovo\n");
+    if (!o.vcfInFile.empty()) throw FatalError("--denovo_carriers is not available with --in_vcf\n");
+    if (o.denovo_carriers < 1 || o.denovo_carriers > 8) throw FatalError("--denovo_carriers takes a person count from 1 to 8\n");
   }
   return o;
 }
@@ -220,16 +226,20 @@ struct Batch {
   pm_geno_call* calls = nullptr;
   std::vector<pm_fam_lr> dnf;   // --denovo_families K: [rows][K] ranked families of the batch's records (by call_row)
   int dnf_k = 0;
+  std::vector<pm_person_dn> dnc;   // --denovo_carriers K: [rows][K] ranked non-founders of the batch's records (by call_row)
+  int dnc_k = 0;
   std::vector<int> pos;
   Batch() = default;
   Batch(const Batch&) = delete;
   Batch& operator=(const Batch&) = delete;
   ~Batch() { release(); }
-  void init(SiteEvaluator& e, int capacity, int nperson, int fam_k = 0) {
+  void init(SiteEvaluator& e, int capacity, int nperson, int fam_k = 0, int person_k = 0) {
     release();
     ev = &e; cap = capacity; np = nperson; n = 0;
     dnf_k = fam_k;
     dnf.assign((size_t)cap * dnf_k, pm_fam_lr{-1, 0, 0.0});
+    dnc_k = person_k;
+    dnc.assign((size_t)cap * dnc_k, pm_person_dn{-1, -1, -1, -1, 0, 0.0});
     pl = (uint8_t*)e.host_alloc((size_t)cap * np * 10);
     dm = (uint32_t*)e.host_alloc((size_t)cap * np * 4);
     ref = (uint8_t*)e.host_alloc((size_t)cap);
@@ -241,7 +251,11 @@ struct Batch {
     pos.assign(cap, 0);
   }
   // after the batch's run() / collect(): its ranked families, and the row of a written record
-  void fetch_dnf() { if (dnf_k > 0) ev->denovo_families(dnf.data()); }
+  void fetch_dnf() {
+    if (dnf_k > 0) ev->denovo_families(dnf.data());
+    if (dnc_k > 0) ev->denovo_carriers(dnc.data());
+  }
+  const pm_person_dn* dnc_row(const pm_site_result& r) const { return (dnc_k > 0 && r.call_row >= 0) ? dnc.data() + (size_t)r.call_row * dnc_k : nullptr; }
   const pm_fam_lr* dnf_row(const pm_site_result& r) const { return (dnf_k > 0 && r.call_row >= 0) ? dnf.data() + (size_t)r.call_row * dnf_k : nullptr; }
   void release() {
     if (!ev) return;
@@ -300,8 +314,9 @@ int run_polymutt_sharded(const Options& opt, const Pedigree& ped, SiteEvaluator&
   VcfWriter W;
   W.fh = fh; W.ped = &ped; W.cmd = opt.cmd; W.minMapQuality = opt.minMapQuality; W.minTotalDepth = opt.minTotalDepth;
   W.maxTotalDepth = opt.maxTotalDepth; W.posterior = opt.posterior; W.gl_off = opt.gl_off; W.force_call = opt.force_call;
-  W.denovo = opt.denovo; W.dnf_k = opt.denovo_families;
+  W.denovo = opt.denovo; W.dnf_k = opt.denovo_families; W.dnc_k = opt.denovo_carriers;
   if (opt.denovo_families > 0) eval.set_denovo_families(opt.denovo_families);
+  if (opt.denovo_carriers > 0) eval.set_denovo_carriers(opt.denovo_carriers);
   W.header_written = true;   // parts hold records only
   std::map<std::string, int> chrSel = parse_chr_selection(opt.chrs2process);
   const size_t chrSelCount = chrSel.size();
@@ -309,7 +324,7 @@ int run_polymutt_sharded(const Options& opt, const Pedigree& ped, SiteEvaluator&
   if (lead) printf("Analysis started on %s\n", ctime(&t0));
   const int np = (int)ped.column_pid.size();
   Batch B;
-  B.init(eval, opt.batch > 0 ? opt.batch : 4096, np, opt.denovo_families);
+  B.init(eval, opt.batch > 0 ? opt.batch : 4096, np, opt.denovo_families, opt.denovo_carriers);
   enum { K_ENTRIES = 16, K_OUT, K_REC, K_START, K_END, K_FIRST_END, K_STUCK, K };
   // A Brent stuck at ITMAX (core/MathGold.cpp:98,175) ends the reference's run at that site, every earlier record
   // written, no summary for the section: the stuck shard writes its records before the site, the exchange tells every
@@ -361,7 +376,7 @@ int run_polymutt_sharded(const Options& opt, const Pedigree& ped, SiteEvaluator&
         n_out++;
         const uint8_t* pl = B.pl + (size_t)i * np * 10;
         const uint32_t* dm = B.dm + (size_t)i * np;
-        W.output(label, B.pos[i], B.ref[i], r, r.call_row >= 0 ? B.calls + (size_t)r.call_row * np : nullptr, pl, dm, B.dnf_row(r));
+        W.output(label, B.pos[i], B.ref[i], r, r.call_row >= 0 ? B.calls + (size_t)r.call_row * np : nullptr, pl, dm, B.dnf_row(r), B.dnc_row(r));
         if (r.emit != 1) continue;
         if (n_rec++ == 0) {   // the shard's first record: keep its site for a possible re-run
           first_end = ftell(fh);
@@ -420,13 +435,16 @@ int run_polymutt_sharded(const Options& opt, const Pedigree& ped, SiteEvaluator&
       eval.run(1, fpl.data(), fdm.data(), &fref, &r1, c1.data(), &rows);
       std::vector<pm_fam_lr> d1((size_t)std::max(1, opt.denovo_families), pm_fam_lr{-1, 0, 0.0});
       if (opt.denovo_families > 0) eval.denovo_families(d1.data());
+      std::vector<pm_person_dn> c1d((size_t)std::max(1, opt.denovo_carriers), pm_person_dn{-1, -1, -1, -1, 0, 0.0});
+      if (opt.denovo_carriers > 0) eval.denovo_carriers(c1d.data());
       char* buf = nullptr;
       size_t len = 0;
       FILE* ms = open_memstream(&buf, &len);
       VcfWriter W1 = W;
       W1.fh = ms;
       W1.output(label, fpos, fref, r1, r1.call_row >= 0 ? c1.data() : nullptr, fpl.data(), fdm.data(),
-                (opt.denovo_families > 0 && r1.call_row >= 0) ? d1.data() : nullptr);
+                (opt.denovo_families > 0 && r1.call_row >= 0) ? d1.data() : nullptr,
+                (opt.denovo_carriers > 0 && r1.call_row >= 0) ? c1d.data() : nullptr);
       fclose(ms);
       FILE* fx = fopen((part + ".fix" + std::to_string(secs.size())).c_str(), "wb");
       if (!fx) { free(buf); throw FatalError("vcfOutFile can not be opened for output!\n"); }
@@ -533,8 +551,9 @@ int run_polymutt(const Options& opt, const Pedigree& ped, SiteEvaluator& eval, c
   VcfWriter W;
   W.fh = vcf; W.ped = &ped; W.cmd = opt.cmd; W.minMapQuality = opt.minMapQuality; W.minTotalDepth = opt.minTotalDepth;
   W.maxTotalDepth = opt.maxTotalDepth; W.posterior = opt.posterior; W.gl_off = opt.gl_off; W.force_call = opt.force_call;
-  W.denovo = opt.denovo; W.dnf_k = opt.denovo_families;
+  W.denovo = opt.denovo; W.dnf_k = opt.denovo_families; W.dnc_k = opt.denovo_carriers;
   if (opt.denovo_families > 0) eval.set_denovo_families(opt.denovo_families);
+  if (opt.denovo_carriers > 0) eval.set_denovo_carriers(opt.denovo_carriers);
 
   std::map<std::string, int> chrSel = parse_chr_selection(opt.chrs2process);
   const size_t chrSelCount = chrSel.size();
@@ -571,7 +590,7 @@ int run_polymutt(const Options& opt, const Pedigree& ped, SiteEvaluator& eval, c
     Channel<Batch*> freeq;
     for (int i = 0; i < 3 + std::max(1, eval.in_flight()); i++) {
       pool.emplace_back(new Batch);
-      pool.back()->init(eval, cap, np, opt.denovo_families);
+      pool.back()->init(eval, cap, np, opt.denovo_families, opt.denovo_carriers);
       freeq.push(pool.back().get());
     }
     Channel<Msg> toEngine, toWriter;
@@ -669,7 +688,7 @@ int run_polymutt(const Options& opt, const Pedigree& ped, SiteEvaluator& eval, c
                 const int i = recs[k];
                 const pm_site_result& r = b.res[i];
                 W.format(out, m.label, b.pos[i], b.ref[i], r, b.calls + (size_t)r.call_row * np, b.pl + (size_t)i * np * 10,
-                         b.dm + (size_t)i * np, b.dnf_row(r));
+                         b.dm + (size_t)i * np, b.dnf_row(r), b.dnc_row(r));
               }
             };
             if (nc > 1) fmt_pool.run(nc, format_chunk);
@@ -759,7 +778,7 @@ int run_polymutt(const Options& opt, const Pedigree& ped, SiteEvaluator& eval, c
     return 0;
   }
 
-  B.init(eval, opt.batch > 0 ? opt.batch : 4096, np, opt.denovo_families);
+  B.init(eval, opt.batch > 0 ? opt.batch : 4096, np, opt.denovo_families, opt.denovo_carriers);
   while (src.nextSection()) {
     if (!chrSel.empty() && chrDone >= chrSelCount) break;
     const std::string label = src.label();
@@ -789,7 +808,7 @@ int run_polymutt(const Options& opt, const Pedigree& ped, SiteEvaluator& eval, c
         const pm_site_result& r = B.res[i];
         if (!r.emit) continue;
         W.output(label, B.pos[i], B.ref[i], r, r.call_row >= 0 ? B.calls + (size_t)r.call_row * np : nullptr, B.pl + (size_t)i * np * 10,
-                 B.dm + (size_t)i * np, B.dnf_row(r));
+                 B.dm + (size_t)i * np, B.dnf_row(r), B.dnc_row(r));
         out_cnt++;
         if (opt.force_call && out_cnt >= (int)positionMap.size()) stop = true;   // main.cpp:593 returns without a summary
       }

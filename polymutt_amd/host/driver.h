@@ -28,6 +28,10 @@ struct Options {
   // --denovo_families K: de novo records name the K families (1..8) with the largest share of DQ (INFO tags DNF / DNFLR)
   int denovo_families = 0;
   bool denovo_families_given = false;
+  // --denovo_carriers K: de novo records name the K non-founders (1..8) most likely to carry a de novo mutation, with
+  // their posterior and most likely event (INFO tags DNC / DNCP / DNCE)
+  int denovo_carriers = 0;
+  bool denovo_carriers_given = false;
   std::string cmd;
   pm_params params() const;
 };
@@ -76,6 +80,9 @@ class SiteEvaluator {
   // another one.  Only the GPU engine computes them.
   virtual void set_denovo_families(int top_k) { (void)top_k; throw FatalError("--denovo_families needs the GPU engine\n"); }
   virtual void denovo_families(pm_fam_lr* top) { (void)top; throw FatalError("--denovo_families needs the GPU engine\n"); }
+  // --denovo_carriers: the same protocol with the rows [rows][K] of ranked non-founders
+  virtual void set_denovo_carriers(int top_k) { (void)top_k; throw FatalError("--denovo_carriers needs the GPU engine\n"); }
+  virtual void denovo_carriers(pm_person_dn* top) { (void)top; throw FatalError("--denovo_carriers needs the GPU engine\n"); }
   // Host memory for the batch buffers (the engine: page-locked, for asynchronous copies)
   virtual void* host_alloc(size_t bytes);
   virtual void host_free(void* p);

@@ -108,6 +108,13 @@ class EngineEvaluator : public SiteEvaluator {
     if (!last_) throw FatalError("GPU engine error: no finished batch\n");
     check(pm_engine_denovo_families(last_, top, nullptr, nullptr));
   }
+  void set_denovo_carriers(int top_k) override {
+    for (auto* e : eng_) check(pm_engine_set_denovo_carriers(e, top_k, 0));
+  }
+  void denovo_carriers(pm_person_dn* top) override {
+    if (!last_) throw FatalError("GPU engine error: no finished batch\n");
+    check(pm_engine_denovo_carriers(last_, top, nullptr));
+  }
   void* host_alloc(size_t bytes) override {
     void* p = nullptr;
     if (pm_host_alloc(bytes ? bytes : 1, &p) != PM_OK || !p) return SiteEvaluator::host_alloc(bytes);   // pageable fallback

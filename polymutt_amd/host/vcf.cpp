@@ -33,6 +33,11 @@ void VcfWriter::header() {
     fprintf(fh, "##INFO=<ID=DNF,Number=.,Type=String,Description=\"Families With the Largest Shares of DQ, Largest First\">\n");
     fprintf(fh, "##INFO=<ID=DNFLR,Number=.,Type=Float,Description=\"Share of DQ (log10 Likelihood Ratio) of Each DNF Family\">\n");
   }
+  if (denovo && dnc_k > 0) {
+    fprintf(fh, "##INFO=<ID=DNC,Number=.,Type=String,Description=\"Persons Most Likely to Carry a De Novo Mutation, Most Likely First\">\n");
+    fprintf(fh, "##INFO=<ID=DNCP,Number=.,Type=Float,Description=\"Posterior Probability of a De Novo Mutation in Each DNC Person\">\n");
+    fprintf(fh, "##INFO=<ID=DNCE,Number=.,Type=String,Description=\"Most Likely Event of Each DNC Person, FatherxMother>Child Genotypes\">\n");
+  }
   fprintf(fh, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n");
   fprintf(fh, "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype Quality\">\n");
   fprintf(fh, "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Read Depth\">\n");
@@ -47,17 +52,18 @@ void VcfWriter::header() {
 }
 
 void VcfWriter::output(const std::string& label, int pos1, int refBase, const pm_site_result& r, const pm_geno_call* calls,
-                       const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf) {
+                       const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf, const pm_person_dn* dnc) {
   if (!header_written) header();
   if (r.emit != 1) return;   // OutputVCF_denovo returns before the record when denovoLR < minLLR (:1868)
   line_.clear();
-  format(line_, label, pos1, refBase, r, calls, pl, dm, dnf);
+  format(line_, label, pos1, refBase, r, calls, pl, dm, dnf, dnc);
   fwrite(line_.data(), 1, line_.size(), fh);
   fflush(fh);
 }
 
 void VcfWriter::format(std::string& L, const std::string& label, int pos1, int refBase, const pm_site_result& r,
-                       const pm_geno_call* calls, const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf) const {
+                       const pm_geno_call* calls, const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf,
+                       const pm_person_dn* dnc) const {
   const int n = (int)ped->column_pid.size();
   const bool refIsA1 = refBase == r.allele1;
   char info[512], head[1024];
@@ -142,6 +148,20 @@ void VcfWriter::format(std::string& L, const std::string& label, int pos1, int r
         lrs += v;
       }
       if (!ids.empty()) { L += ";DNF="; L += ids; L += ";DNFLR="; L += lrs; }
+    }
+    if (dnc_k > 0 && dnc) {   // ;DNC=<pid>[,...];DNCP=<%.4g>[,...];DNCE=<fa><mo>><kid>[,...] (entries without a person are not printed)
+      static const char* g2[10] = {"AA", "AC", "AG", "AT", "CC", "CG", "CT", "GG", "GT", "TT"};
+      auto gs = [&](int g) { return (g >= 0 && g < 10) ? g2[g] : ".."; };
+      std::string ids, pps, evs;
+      for (int k = 0; k < dnc_k && dnc[k].person >= 0 && dnc[k].person < n; k++) {
+        char v[64];
+        snprintf(v, sizeof(v), "%.4g", dnc[k].pp);
+        if (k) { ids += ','; pps += ','; evs += ','; }
+        ids += ped->column_pid[dnc[k].person];
+        pps += v;
+        evs += gs(dnc[k].fa_g); evs += 'x'; evs += gs(dnc[k].mo_g); evs += '>'; evs += gs(dnc[k].kid_g);
+      }
+      if (!ids.empty()) { L += ";DNC="; L += ids; L += ";DNCP="; L += pps; L += ";DNCE="; L += evs; }
     }
     L += gl_off ? "\tGT:GQ:DP" : "\tGT:GQ:DP:PL";
     const size_t at = L.size();

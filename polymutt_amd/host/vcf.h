@@ -19,16 +19,18 @@ struct VcfWriter {
   bool header_written = false;
   int chrom = PM_CHR_AUTO;
   int dnf_k = 0;               // --denovo_families K: INFO gains DNF (family ids) and DNFLR (their shares of DQ) after DQ
+  int dnc_k = 0;               // --denovo_carriers K: INFO gains DNC (person ids), DNCP (posteriors) and DNCE (events) after those
 
   // One OutputVCF(_denovo) call: writes the header on first use, then the record unless suppressed.
   // dnf: the record's dnf_k ranked families (pm_engine_denovo_families; required when dnf_k > 0)
+  // dnc: the record's dnc_k ranked non-founders (pm_engine_denovo_carriers; required when dnc_k > 0)
   void output(const std::string& label, int pos1, int refBase, const pm_site_result& r, const pm_geno_call* calls,
-              const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf = nullptr);
+              const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf = nullptr, const pm_person_dn* dnc = nullptr);
   void header();   // written by output() on first use; a sharded run's lead writes it once at the merge
   // The record text of an emitted site (r.emit == 1) appended to `out`, as output() writes it (no header, no I/O;
   // safe to call from several threads at once: the pipelined CLI formats a batch's records in parallel)
   void format(std::string& out, const std::string& label, int pos1, int refBase, const pm_site_result& r,
-              const pm_geno_call* calls, const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf = nullptr) const;
+              const pm_geno_call* calls, const uint8_t* pl, const uint32_t* dm, const pm_fam_lr* dnf = nullptr, const pm_person_dn* dnc = nullptr) const;
 
  private:
   bool singleNuclear() const;
