@@ -964,7 +964,7 @@ static const pmjit::Kernel* jit_kernel(pm_engine* E) {
     const int dmode = !E->par.denovo ? 0 : (!E->vcf && !getenv("PM_ES_NOGROUP")) ? 2 : 1;
     if (!fams.empty() && pmjit::build(E->device, cls, fams, kTBA, dmode, &K, &err)) {
       const size_t ns = K.slot_e.size();
-      std::vector<int> tab(3 * ns + K.pair_k.size());   // slot_e | slot_sig | slot_p0 | pair_k (pair mode)
+      std::vector<int> tab(3 * ns + K.pair_k.size());   // slot_e | slot_sig | slot_p0 | pair_k (es_hoist_wave)
       for (size_t i = 0; i < ns; i++) { tab[i] = K.slot_e[i]; tab[ns + i] = K.slot_sig[i]; tab[2 * ns + i] = K.slot_p0[i]; }
       std::copy(K.pair_k.begin(), K.pair_k.end(), tab.begin() + 3 * ns);
       if (dalloc(&E->d_jit_slots[plan][cls], tab.size()) == PM_OK &&
@@ -1219,9 +1219,8 @@ static int launch_brent(pm_engine* E, const DevArgs& A0, int list, bool unrelate
         if (K->wave)
           HIP_TRY(hipModuleLaunchKernel(K->fn, E->n_cu * (K->blocks_per_cu > 0 ? K->blocks_per_cu : std::max(1, 16 / K->wpb)), 1, 1,
                                         64 * K->wpb, 1, 1, 0, E->stream, params, nullptr));
-        else   // (a persistent grid of the resident blocks: each thread loads its next unit's PL bytes ahead)
-          HIP_TRY(hipModuleLaunchKernel(K->fn, E->n_cu * (K->blocks_per_cu > 0 ? std::min(8, K->blocks_per_cu) : 8), 1, 1, 256, 1, 1, 0,
-                                        E->stream, params, nullptr));
+        else
+          HIP_TRY(hipModuleLaunchKernel(K->fn, E->n_cu * 8, 1, 1, 256, 1, 1, 0, E->stream, params, nullptr));
       } else hipLaunchKernelGGL(hoist, dim3(hgrid), dim3(64 * E->hoist_waves), hlds, E->stream, A, list);
       HIP_TRY(hipGetLastError());
       if ((mrc = mark(E->es_events, false))) return mrc;

@@ -3,6 +3,7 @@
 #include <hip/hiprtc.h>
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -100,9 +101,6 @@ std::string shape_key(const Family& F) {
   return k;
 }
 
-int g_bapf = 0;           // es_hoist_jit: PL bytes of the thread's next (item, family) loaded ahead, 3 per person of the
-                          // largest family (0: off, the default -- PM_ES_BAPF=1 turns it on for families of <= 12)
-
 // One family shape's hoisting as a device function: the polynomial of FamilyLikelihoodES' BA peel in (f, g).
 // fused: the ep_brent_jit form -- inlined, the D + 1 coefficients into the caller's register array out[0..D] (no degree
 // word); *deg = D.
@@ -117,8 +115,7 @@ std::string gen_family(const Family& F, int chrom, const double (*T)[27], const 
     auto it = pen.find(key);
     if (it != pen.end()) return it->second;
     static const char* plane[3] = {"P11", "P12", "P22"};
-    std::string v = g_bapf ? G.def("lk[b[" + std::to_string(3 * i + j) + "]]")
-                           : G.def(std::string("lk[") + plane[j] + "[p0 + " + std::to_string(i) + "]]");
+    std::string v = G.def(std::string("lk[") + plane[j] + "[p0 + " + std::to_string(i) + "]]");
     pen[key] = v;
     return v;
   };
@@ -195,13 +192,10 @@ std::string gen_family(const Family& F, int chrom, const double (*T)[27], const 
     for (int a = 0; a <= L.d; a++) out += "  out[" + std::to_string(a) + "] = " + (L.c[a].empty() ? "0.0" : L.c[a]) + ";\n";
     return out + "}\n";
   }
-  std::string out = g_bapf ? "__device__ __forceinline__ void " + name +   // (inlined: b stays in registers)
-                                 "(const unsigned int* b, const double* __restrict__ lk, double* __restrict__ out, int os, int dcap) {\n" +
-                                 G.code
-                           : "__device__ __attribute__((noinline)) void " + name +
-                                 "(const unsigned char* __restrict__ P11, const unsigned char* __restrict__ P12, "
-                                 "const unsigned char* __restrict__ P22, int p0, const double* __restrict__ lk, double* __restrict__ out, "
-                                 "int os, int dcap) {\n" + G.code;
+  std::string out = "__device__ __attribute__((noinline)) void " + name +
+                    "(const unsigned char* __restrict__ P11, const unsigned char* __restrict__ P12, "
+                    "const unsigned char* __restrict__ P22, int p0, const double* __restrict__ lk, double* __restrict__ out, "
+                    "int os, int dcap) {\n" + G.code;
   for (int a = 0; a <= L.d; a++) out += "  out[" + std::to_string(a) + " * os] = " + (L.c[a].empty() ? "0.0" : L.c[a]) + ";\n";
   out += "  out[(dcap - 1) * os] = " + std::to_string(L.d) + ".0;\n}\n";
   return out;
@@ -233,56 +227,6 @@ __device__ __forceinline__ void cfg_alleles(int cfg, int r, int* a1, int* a2) { 
 )";
 
 std::string gen_kernel(const std::vector<std::string>& shapes) {
-  if (g_bapf) {   // the next unit's PL bytes are loaded before this unit is computed (one HBM round trip hidden per unit)
-    std::string s = R"(
-extern "C" __global__ void __launch_bounds__(256) es_hoist_jit(Args A) {
-  __shared__ double lk[256];
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) lk[i] = A.lktab[i];
-  __syncthreads();
-  const int nItems = min(A.counts[A.list], A.it1);
-  if (nItems <= A.it0) return;
-  const long long units = (long long)(nItems - A.it0) * A.nslots;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  unsigned int bn[NB];
-  // unit uu's bytes b[3 i + j] = plane j (g11, g12, g22) of the family's person i (persons past the family: clamped reads
-  // inside the site's block, never used)
-  auto load = [&](long long uu) {
-    const int uq = (int)(uu / A.nslots), k = (int)(uu - (long long)uq * A.nslots);
-    const int item = A.items[A.it0 + uq];
-    const int site = item >> 3, cfg = item & 7, r = A.ref[site];
-    int a1, a2;
-    if (A.vcf) { a1 = r & 15; a2 = r >> 4; }
-    else if (cfg == 7) { a1 = A.res[(size_t)site * A.res_words + A.res_a1]; a2 = A.res[(size_t)site * A.res_words + A.res_a2]; }
-    else cfg_alleles(cfg, r, &a1, &a2);
-    const uint8_t* pl = A.pl + (size_t)site * A.np * 10;
-    const uint8_t* P[3] = {pl + (size_t)gi(a1, a1) * A.np, pl + (size_t)gi(a1, a2) * A.np, pl + (size_t)gi(a2, a2) * A.np};
-    const int p0 = A.slot_p0[k];
-#pragma unroll
-    for (int i = 0; i < NB / 3; i++) {
-      const int pi = min(p0 + i, A.np - 1);
-#pragma unroll
-      for (int j = 0; j < 3; j++) bn[3 * i + j] = P[j][pi];
-    }
-  };
-  long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (u < units) load(u);
-  for (; u < units; u += stride) {
-    unsigned int b[NB];
-#pragma unroll
-    for (int i = 0; i < NB; i++) b[i] = bn[i];
-    const int uq = (int)(u / A.nslots), k = (int)(u - (long long)uq * A.nslots);
-    const int e = A.slot_e[k], q = e / A.T;
-    double* out = A.coef + ((size_t)uq * A.max_ext + q) * A.dcap * A.T + (e - q * A.T);
-    const int sig = A.slot_sig[k];
-    if (u + stride < units) load(u + stride);
-    switch (sig) {
-)";
-    for (size_t i = 0; i < shapes.size(); i++)
-      s += "      case " + std::to_string(i) + ": " + shapes[i] + "(b, lk, out, A.T, A.dcap); break;\n";
-    s += "    }\n  }\n}\n";
-    for (size_t at; (at = s.find("NB")) != std::string::npos;) s.replace(at, 2, std::to_string(g_bapf));
-    return s;
-  }
   std::string s = R"(
 extern "C" __global__ void __launch_bounds__(256) es_hoist_jit(Args A) {
   __shared__ double lk[256];
@@ -507,296 +451,235 @@ extern "C" __global__ void __launch_bounds__(256) es_post_jit(PostArgs A) {
 
 // ---------------------------------------------------------------------------------------------------------------
 // Wave-cooperative hoisting (--denovo engines: 10-state peels, whose marriage partials -- 100 entries x coefficients
-// -- do not fit one thread's registers).  One (item, family) per wave, as engine.hip's generic k_es_hoist, but
-// compiled per family shape: the workspace layout, every step's degrees and every loop bound are constants, so a
-// phase is a few unrolled multiply-adds per lane between wave-level barriers, with no schedule or layout loads
+// -- do not fit one thread's registers).  One (item, family) per half-wave, as engine.hip's generic k_es_hoist per
+// wave, but compiled per family shape: the workspace layout, every step's degrees and every loop bound are constants,
+// so a phase is a few unrolled multiply-adds per lane between wave-level barriers, with no schedule or layout loads
 // and no run-time divisions.  Variants per shape: 10-state (de novo items), bi-allelic (cfg-7 items), and "top"
 // (the de novo monomorphism item: the f^D coefficient only, every degree 0).
-// The de novo transmission rows of a type-1 step's pairs: from the (cache-resident) global table, or held in 20
-// registers for the whole kernel (PM_ES_TR=reg: 149 VGPRs, 3 waves per SIMD; capped at 128 with 19 spilled)
-bool g_tr_regs = false;
-bool g_prof = false;   // PM_ES_PROF=1: es_hoist_wave accumulates per-part clock cycles into Args::prof
-bool g_pack = true;    // PM_ES_PACK=0: independent type-2 steps one phase each
-// PM_ES_REGP: how a type-1 phase reads the offspring coefficients a preceding type-2 phase computed -- 0 from LDS,
-// 1 all by v_readlane (the non-founder is then never stored), 2 (default) every other offspring of a run by
-// v_readlane and the rest from LDS: the readlanes are VALU work and the LDS reads LDS work, and the two pipes are
-// best balanced half and half (ext10: 0.667 / 0.617 / 0.555 ms per hoisting launch)
-int g_regp = 2;
-bool g_regf = true;    // PM_ES_REGF=0: pristine founders stored and read from LDS (with PM_ES_REGP != 0)
-int g_expt = 0;        // PM_ES_EXPT=1/2: timing experiments only (results wrong), see the uses
-// Family pairs (PM_ES_PAIR, default on): each half-wave (32 lanes) hoists one family of a pair of same-shape families
-// of the task, so every phase whose elements fit 32 lanes (type-2 steps over 10 states, founder-sparse type-1 runs
-// over 30 pairs, the final sum) does two families' work per instruction; g_wl = the lanes per family (64 or 32).
-// Pair mode reads partials across lanes through LDS only (no v_readlane from fixed lanes: PM_ES_REGP / REGF off).
-bool g_pair = false;
-// families per wave (PM_ES_FPW: 1, 2 -- the pair mode above -- or 4): g_wl = 64 / g_fpw lanes per family
-int g_fpw = 1;
-bool g_wspack = true;     // PM_ES_WSPACK=0: part-2 regions laid out in order instead of packed by live range
-bool g_fence = true;      // PM_ES_FENCE=0: wave_sync without the wavefront-scope fences (measured 2% slower)
-bool g_xcd = true;        // PM_ES_XCD=0: units dealt to the blocks in plain order
-bool g_no_penp = false;   // PM_ES_PENP=0: leaf offspring partials stored and read from the workspace
-// dense 10-state type-3 steps with a marriage partial (the plain transmission, quirk :1391): each child state's sum runs
-// over its non-zero parent pairs from an LDS list (t3z / t3n, filled from kT3z / kT3n at kernel start); g_t3z: some
-// family of the kernel uses it (PM_ES_T3Z=0, g_no_t3z: the 100-pair loop over the global table)
-bool g_t3z = false;
-bool g_no_t3z = false;
-int g_wl = 64;
-// PM_ES_FACT=1 (opt-in experiment): a dense 10-state type-1 run through T10dn = T10 * M (SetTransmissionMatrix_denovo
-// :787-810) -- P' = M P per offspring coefficient (lanes over (genotype, coefficient)), then per pair 0.25 x the sum
-// of P' at its four Mendelian children, instead of sum_k T10dn(e, k) P(k): the same value in real arithmetic, a
-// different rounding order (not the reference's), ~3x fewer operations and no per-lane transmission-row loads
-bool g_fact = false;
+//
+// The one configuration (the measured-and-rejected alternatives are in the history):
+//  * family pairs: each half-wave (kWl = 32 lanes) hoists one of two same-shape families of the task in its own
+//    workspace slice, so every phase whose elements fit 32 lanes (type-2 steps over 10 states, founder-sparse type-1
+//    runs over 30 pairs, the final sum) does two families' work per instruction;
+//  * partials are read across lanes through LDS only;
+//  * a founder read only by pristine type-2 steps is never stored: its terms read the penetrance from PEN;
+//  * a person first used as the to-person of a type-2 step has its initial partial formed in that step's lanes;
+//  * independent type-2 steps of one shape share a phase, 16 lanes each;
+//  * the per-item rest's regions are packed by live range.
+constexpr int kFpw = 2;          // families per wave
+constexpr int kWl = 64 / kFpw;   // lanes per family
 
-struct WaveGen {
-  std::string code;
-  void loop(int N, const std::string& body) {   // lanes over N elements x, then a wave barrier
-    code += "  for (int x = lane; x < " + std::to_string(N) + "; x += 64) {\n" + body + "  }\n  wave_sync();\n";
-  }
+// The generator's switches: generate() fills them from the environment and passes them down
+struct Opts {
+  bool prof = false;     // PM_ES_PROF=1: es_hoist_wave accumulates per-part clock cycles into Args::prof
+  bool sp3 = true;       // PM_ES_SP3=0: type-3 steps with a founder parent over all 100 pairs
+  bool t3z = true;       // PM_ES_T3Z=0: dense type-3 child sums over all 100 parent pairs of the global table
+  bool layout = false;   // PM_JIT_LAYOUT: workspace layouts and static lane occupancy to stderr
+  bool steps = false;    // PM_JIT_STEPS: every step's operations to stderr
 };
 
-// ops: the FP64 operations the generated phases perform (summed over their work elements: the useful lane-operations,
-// whatever the lanes' occupancy)
+std::string S(long v) { return std::to_string(v); }
+
+struct StepDeg { int a, b, c, e; };
+// the founder-sparse rows of a type-1 run (sparse_of): the founder's non-zero states, its side of the pair, compact rows
+struct Sparse { std::vector<std::pair<int, int>> terms; bool father = false, compact = false; };
+
+// What the generated function of one (family shape, variant, part) depends on: degrees, classifications and the
+// workspace layout.  analyse_wave_family() fills it; the emit_* functions below only read it.
 // part (10-state variants only): 0 the whole peel; 1 the cfg-independent prefix -- the 10-state penetrances of
 // non-founders no step changes and the type-1 steps that peel them into marriage partials no cfg-dependent step
 // writes (leaf steps, run first: nothing they read or write is touched by an earlier step) -- and 2 the rest (the
 // other persons' partials, the other steps, the final sum).  Part 1 once and part 2 per item give part 0's values for
 // the de novo items of one site (they differ only in the founder priors' genotypes; the top variant's leaf steps are
 // the same degree-0 products).  Parts lay out the workspace by the 10-state variant's degrees, top or not.
-std::string gen_wave_family(const Family& F, int chrom, int NS, bool top, const std::string& name, int* ws_doubles, double* ops,
-                            int part = 0, int multi = 1) {
-  const int n = F.n;
-  const bool X = chrom == PM_CHR_X, Y = chrom == PM_CHR_Y, MT = chrom == PM_CHR_MT;
-  // degrees through the peel (poly_layout's rule), capacities, temporaries (type 3 only: the W(i, j) products)
-  std::vector<int> d0(n), dP(n), capP(n);
-  std::map<int, int> dM, capM;
-  int tmp = 1;
-  // founder-sparse type-3 steps (see sp3): 10 states, one item per call, not switched off (PM_ES_SP3=0)
-  const char* es3 = getenv("PM_ES_SP3");
-  const bool sp3_on = NS == 10 && !(part == 2 && std::max(1, multi) > 1) && !(es3 && es3[0] == '0');
-  struct StepDeg { int a, b, c, e; };
-  std::vector<StepDeg> sd;
-  for (int pass = (part && top) ? 0 : 1; pass < 2; pass++) {   // (pass 0: the 10-state variant's capacities)
-  const bool tp = pass == 1 && top;
-  sd.clear(); dM.clear();
-  for (int i = 0; i < n; i++) {
-    const bool fo = F.founder[i] && i < F.nf;
-    const int sx = F.sex[i];
-    const int dfull = !fo ? 0 : (Y && sx == FEMALE) ? 0 : (((X || Y) && sx == MALE) || MT) ? 1 : 2;
-    d0[i] = dP[i] = tp ? 0 : dfull;
-    capP[i] = std::max(pass ? capP[i] : 0, dP[i] + 1);
+struct WaveFamily {
+  const Family& F;
+  int chrom, NS;
+  bool top;
+  int part;
+  std::string name;
+  int n, nst;
+  std::vector<int> d0, dP, capP;   // persons: initial and final degree, capacity (coefficients per state)
+  std::map<int, int> capM;         // marriage slots: capacity
+  int tmp = 1;                     // the type-3 products W(i, j)
+  std::vector<StepDeg> sd;         // the steps' operand degrees
+  // leaf steps (part 1) and the persons only they read; pristine[k]: the founder "from" of type-2 step k still holds
+  // its prior x penetrance partial (3 non-zero states), so the step sums over those 3 states only; sp3[k]: a
+  // founder-sparse type-3 step
+  std::vector<char> leaf, leafp, pristine, sp3;
+  // persons without a workspace region: penf, founders read only through pristine type-2 steps (the terms read PEN);
+  // penp, leaf offspring (the leaf steps read PEN); iinit, persons whose initial partial their type-2 step forms
+  std::vector<char> penf, penp, iinit;
+  std::map<int, int> crows;        // compactly stored marriage partials: slot -> rows
+  std::map<int, int> leafs;        // the marriage slots the leaf steps write
+  std::vector<int> po;             // offsets: persons
+  std::map<int, int> mo;           // marriage slots
+  int LSZ = 0, NSZ = 0, TB = 0;    // the leaf prefix's doubles, the rest's, the type-3 products' offset
+  int ws = 0;                      // workspace doubles
+
+  int type(int k) const { return F.steps[k].x & 255; }
+  int from0(int k) const { return (F.steps[k].x >> 8) & 255; }
+  int from1(int k) const { return (F.steps[k].x >> 16) & 255; }
+  int to0(int k) const { return (F.steps[k].x >> 24) & 255; }
+  int slot(int k) const { return (F.steps[k].y >> 8) & 255; }
+  bool create(int k) const { return (F.steps[k].y >> 16) & 1; }
+  bool fa2mo(int k) const { return (F.steps[k].y >> 17) & 1; }
+  bool founder(int i) const { return F.founder[i] && i < F.nf; }
+  int fdeg(int i) const {   // a founder's prior degree (SetFounderPriors)
+    const bool X = chrom == PM_CHR_X, Y = chrom == PM_CHR_Y, MT = chrom == PM_CHR_MT;
+    return (Y && F.sex[i] == FEMALE) ? 0 : (((X || Y) && F.sex[i] == MALE) || MT) ? 1 : 2;
   }
-  for (const int2& S : F.steps) {
-    const int type = S.x & 255, from0 = (S.x >> 8) & 255, from1 = (S.x >> 16) & 255, to0 = (S.x >> 24) & 255;
-    const int slot = (S.y >> 8) & 255, create = (S.y >> 16) & 1;
-    StepDeg g{0, 0, 0, 0};
-    if (type == 1) {
-      g.a = dP[from0]; g.b = create ? 0 : dM[slot];
-      dM[slot] = g.a + g.b;
-      capM[slot] = std::max(capM[slot], dM[slot] + 1);
-    } else if (type == 2) {
-      g.a = dP[from0]; g.b = slot == 255 ? 0 : dM[slot]; g.c = dP[to0];
-      dP[to0] = g.a + g.b + g.c;
-      capP[to0] = std::max(capP[to0], dP[to0] + 1);
-    } else {
-      g.a = dP[from0]; g.b = slot == 255 ? 0 : dM[slot]; g.c = dP[from1]; g.e = dP[to0];
-      dP[to0] = g.a + g.b + g.c + g.e;
-      capP[to0] = std::max(capP[to0], dP[to0] + 1);
-      // (the W(i, j) products: a founder-sparse step -- sp3 below -- keeps only its supports' pairs; pterms' sizes)
-      auto supp = [&](int f) {
-        if (!(NS == 10 && sp3_on && F.founder[f] && f < F.nf)) return NS;
-        const int sx = F.sex[f];
-        const int dfull = (Y && sx == FEMALE) ? 0 : (((X || Y) && sx == MALE) || MT) ? 1 : 2;
-        return top ? (dfull > 0 ? 1 : 3) : dfull == 1 ? 2 : 3;
-      };
-      tmp = std::max(tmp, supp(from0) * supp(from1) * (g.a + g.b + g.c + 1));
-    }
-    sd.push_back(g);
-  }
-  }
-  // leaf steps (part 1) and the persons only they read; pristine[s]: the founder "from" of step s still holds its
-  // prior x penetrance partial (3 non-zero states), so a type-2 step sums over those 3 states only
-  const int nst = (int)F.steps.size();
-  std::vector<char> leaf(nst, 0), leafp(n, 0), pristine(nst, 0);
-  if (NS == 10) {
-    auto ty = [&](int k) { return F.steps[k].x & 255; };
-    auto fr = [&](int k) { return (F.steps[k].x >> 8) & 255; };
-    auto to = [&](int k) { return (F.steps[k].x >> 24) & 255; };
-    auto sl = [&](int k) { return (F.steps[k].y >> 8) & 255; };
-    auto fo = [&](int i) { return F.founder[i] && i < F.nf; };
-    std::vector<char> isto(n, 0), touched(n, 0);
-    for (int k = 0; k < nst; k++)
-      if (ty(k) != 1) isto[to(k)] = 1;
-    for (int k = 0; k < nst; k++) {
-      if (ty(k) == 2 && fo(fr(k)) && !touched[fr(k)]) pristine[k] = 1;
-      if (ty(k) != 1) touched[to(k)] = 1;
-      // a leaf step reads a non-founder's penetrance partial that no step ever changes
-      if (ty(k) == 1 && !fo(fr(k)) && !isto[fr(k)]) leaf[k] = 1;
-    }
-    // ... into a marriage partial that only leaf steps write, and that no step reads before the last of them
-    for (bool changed = true; changed;) {
-      changed = false;
-      std::map<int, int> nonleaf_writer;
-      for (int k = 0; k < nst; k++)
-        if (ty(k) == 1 && !leaf[k]) nonleaf_writer[sl(k)] = 1;
-      for (int k = 0; k < nst; k++) {
-        if (leaf[k] && nonleaf_writer.count(sl(k))) { leaf[k] = 0; changed = true; }
-        if (ty(k) == 1 || sl(k) == 255) continue;
-        for (int k2 = k + 1; k2 < nst; k2++)
-          if (leaf[k2] && ty(k2) == 1 && sl(k2) == sl(k)) { leaf[k2] = 0; changed = true; }
-      }
-    }
-    for (int k = 0; k < nst; k++)
-      if (leaf[k]) leafp[fr(k)] = 1;
-  }
-  // workspace layout: persons' partials, marriage partials, the type-3 products.  Parts put the leaf prefix's
-  // regions first (a task's items share them) and give each of the M items of a part-2 function its own copy of the
-  // rest, cb = c * NSZ doubles further on
+  bool inpart(int k) const { return !((part == 1 && !leaf[k]) || (part == 2 && leaf[k])); }
+  int mcap(int s) const { auto it = capM.find(s); return it == capM.end() ? 0 : it->second; }
+  int mrows(int s) const { auto it = crows.find(s); return it == crows.end() ? NS * NS : it->second; }
+  std::string PO(int i) const { return S(po[i]); }
+  std::string MO(int s) const { auto it = mo.find(s); return S(it == mo.end() ? 0 : it->second); }
   // a pristine founder's non-zero states (q: 0 g11, 1 g12, 2 g22) and their coefficient u, in the dense loop's order
   // of u at one j: prior x penetrance (SetFounderPriors), the top variant's f^D term only
-  auto pterms = [&](int f) {
-    const int sx = F.sex[f];
-    const int dfull = (Y && sx == FEMALE) ? 0 : (((X || Y) && sx == MALE) || MT) ? 1 : 2;
-    std::vector<std::pair<int, int>> t;
-    if (top) {
-      if (dfull > 0) t = {{0, 0}};
-      else t = {{2, 0}, {1, 0}, {0, 0}};
-    } else if (d0[f] == 2) t = {{2, 0}, {1, 1}, {0, 2}};
-    else if (d0[f] == 1) t = {{2, 0}, {0, 1}};
-    else t = {{2, 0}, {1, 0}, {0, 0}};
-    return t;
-  };
+  std::vector<std::pair<int, int>> pterms(int f) const {
+    if (top) return fdeg(f) > 0 ? std::vector<std::pair<int, int>>{{0, 0}} : std::vector<std::pair<int, int>>{{2, 0}, {1, 0}, {0, 0}};
+    if (d0[f] == 2) return {{2, 0}, {1, 1}, {0, 2}};
+    if (d0[f] == 1) return {{2, 0}, {0, 1}};
+    return {{2, 0}, {1, 0}, {0, 0}};
+  }
   // runs of consecutive type-1 steps of this part (one phase each in the 10-state code), and their founder-sparse
   // rows: when a run writes one marriage partial and its only later reader is a pristine type-2 step (the founder
   // spouse F peeled into the other), that step reads the rows of F's non-zero states only (2-3 of 10; 1 in the top
   // variant), so only those pairs are computed (lanes over F's states x the spouse's).  In part 2 a partial whose
   // writers all sit in such a run is stored compactly, row q * 10 + spouse state for F's q-th term.
-  auto inpart = [&](int k2) { return !((part == 1 && !leaf[k2]) || (part == 2 && leaf[k2])); };
-  auto run_of = [&](int k0) {
+  std::vector<int> run_of(int k0) const {
     std::vector<int> run;
     for (int k2 = k0; k2 < nst; k2++) {
       if (!inpart(k2)) continue;
-      if ((F.steps[k2].x & 255) != 1) break;
+      if (type(k2) != 1) break;
       run.push_back(k2);
     }
     return run;
-  };
-  struct Sparse { std::vector<std::pair<int, int>> terms; bool father = false, compact = false; };
-  auto sparse_of = [&](const std::vector<int>& run) {
+  }
+  Sparse sparse_of(const std::vector<int>& run) const {
     Sparse sp;
     if (NS != 10 || part == 1 || run.empty()) return sp;
-    const int sl0 = (F.steps[run[0]].y >> 8) & 255;
+    const int sl0 = slot(run[0]);
     for (int k2 : run)
-      if (((F.steps[k2].y >> 8) & 255) != sl0) return sp;
+      if (slot(k2) != sl0) return sp;
     int readers = 0, rk = -1;
     bool writes_after = false, writes_before = false;
     for (int k2 = run.back() + 1; k2 < nst; k2++) {
-      if (!inpart(k2) || ((F.steps[k2].y >> 8) & 255) != sl0) continue;
-      if ((F.steps[k2].x & 255) == 1) writes_after = true;
+      if (!inpart(k2) || slot(k2) != sl0) continue;
+      if (type(k2) == 1) writes_after = true;
       else { readers++; rk = k2; }
     }
     for (int k2 = 0; k2 < run[0]; k2++)
-      if ((F.steps[k2].x & 255) == 1 && ((F.steps[k2].y >> 8) & 255) == sl0) writes_before = true;
-    if (readers == 1 && !writes_after && (F.steps[rk].x & 255) == 2 && pristine[rk]) {
-      sp.terms = pterms((F.steps[rk].x >> 8) & 255);
-      sp.father = (F.steps[rk].y >> 17) & 1;
-      sp.compact = part == 2 && !writes_before && multi <= 1;
+      if (type(k2) == 1 && slot(k2) == sl0) writes_before = true;
+    if (readers == 1 && !writes_after && type(rk) == 2 && pristine[rk]) {
+      sp.terms = pterms(from0(rk));
+      sp.father = fa2mo(rk);
+      sp.compact = part == 2 && !writes_before;
     }
     return sp;
-  };
-  std::map<int, int> crows;   // compactly stored marriage partials: slot -> rows
-  if (NS == 10 && part == 2)
-    for (int k = 0; k < nst; k++) {
-      if (!inpart(k) || (F.steps[k].x & 255) != 1 || (k > 0 && inpart(k - 1) && (F.steps[k - 1].x & 255) == 1)) continue;
-      const std::vector<int> run = run_of(k);
-      const Sparse sp = sparse_of(run);
-      if (sp.compact) crows[(F.steps[k].y >> 8) & 255] = 10 * (int)sp.terms.size();
-    }
-  const int M = part == 2 ? std::max(1, multi) : 1;
-  if (g_fact && NS == 10 && M == 1)   // (PM_ES_FACT: the P' rows of a dense type-1 run in the temporaries' region)
-    for (int k = 0; k < nst; k++) {
-      if (!inpart(k) || (F.steps[k].x & 255) != 1) continue;
-      const std::vector<int> run = run_of(k);
-      int sz = 0;
-      for (int k2 : run) sz += 10 * (sd[k2].a + 1);
-      tmp = std::max(tmp, sz);
-    }
-  std::map<int, int> leafs;   // the marriage slots the leaf steps write
+  }
+};
+
+// leaf and pristine steps, the compact marriage partials, and the persons that need no workspace region
+void classify_steps(WaveFamily& A) {
+  const int n = A.n, nst = A.nst, NS = A.NS, part = A.part;
+  A.leaf.assign(nst, 0); A.leafp.assign(n, 0); A.pristine.assign(nst, 0);
+  A.penf.assign(n, 0); A.penp.assign(n, 0); A.iinit.assign(n, 0);
+  if (NS != 10) return;
+  std::vector<char> isto(n, 0), touched(n, 0);
   for (int k = 0; k < nst; k++)
-    if (leaf[k]) leafs[(F.steps[k].y >> 8) & 255] = 1;
-  // (computed before the layout: persons never stored get no workspace region)
-  std::vector<char> regf(n, 0), regn(n, 0), iinit(n, 0);
-  // (the initial partials formed in the type-2 lanes need no cross-lane read: pair mode keeps them too)
-  if (NS == 10 && part == 2 && multi <= 1 && (g_regp || g_pair)) {
-    const int finp = (F.steps.back().x >> 24) & 255;
-    // (pair mode: such a founder's terms read its penetrance straight from the PEN table, no v_readlane)
-    for (int i = 0; i < n; i++) regf[i] = ((g_regp && g_regf) || g_pair) && F.founder[i] && i < F.nf && !leafp[i] && i != finp;
+    if (A.type(k) != 1) isto[A.to0(k)] = 1;
+  for (int k = 0; k < nst; k++) {
+    if (A.type(k) == 2 && A.founder(A.from0(k)) && !touched[A.from0(k)]) A.pristine[k] = 1;
+    if (A.type(k) != 1) touched[A.to0(k)] = 1;
+    // a leaf step reads a non-founder's penetrance partial that no step ever changes
+    if (A.type(k) == 1 && !A.founder(A.from0(k)) && !isto[A.from0(k)]) A.leaf[k] = 1;
+  }
+  // ... into a marriage partial that only leaf steps write, and that no step reads before the last of them
+  for (bool changed = true; changed;) {
+    changed = false;
+    std::map<int, int> nonleaf_writer;
+    for (int k = 0; k < nst; k++)
+      if (A.type(k) == 1 && !A.leaf[k]) nonleaf_writer[A.slot(k)] = 1;
     for (int k = 0; k < nst; k++) {
-      if (!inpart(k)) continue;
-      const int ty2 = F.steps[k].x & 255, f0 = (F.steps[k].x >> 8) & 255, f1 = (F.steps[k].x >> 16) & 255, t0 = (F.steps[k].x >> 24) & 255;
-      if (ty2 == 2) { regf[t0] = 0; if (!pristine[k]) regf[f0] = 0; }
-      else if (ty2 == 3) regf[f0] = regf[f1] = regf[t0] = 0;
-      else regf[f0] = 0;
+      if (A.leaf[k] && nonleaf_writer.count(A.slot(k))) { A.leaf[k] = 0; changed = true; }
+      if (A.type(k) == 1 || A.slot(k) == 255) continue;
+      for (int k2 = k + 1; k2 < nst; k2++)
+        if (A.leaf[k2] && A.type(k2) == 1 && A.slot(k2) == A.slot(k)) { A.leaf[k2] = 0; changed = true; }
     }
-    // non-founders whose partial is the penetrance until one type-2 step peels a spouse into it, and is then read
-    // only as a type-1 offspring (by v_readlane from that step's registers): never stored either
-    std::vector<int> t2to(n, 0);
-    for (int i = 0; i < n; i++) regn[i] = !(F.founder[i] && i < F.nf) && !leafp[i] && i != finp;
+  }
+  for (int k = 0; k < nst; k++)
+    if (A.leaf[k]) {
+      A.leafp[A.from0(k)] = 1;
+      A.leafs[A.slot(k)] = 1;
+    }
+  if (part == 2)
     for (int k = 0; k < nst; k++) {
-      if (!inpart(k)) continue;
-      const int ty2 = F.steps[k].x & 255, f0 = (F.steps[k].x >> 8) & 255, f1 = (F.steps[k].x >> 16) & 255, t0 = (F.steps[k].x >> 24) & 255;
-      if (ty2 == 2) { t2to[t0]++; regn[f0] = 0; }
-      else if (ty2 == 3) regn[f0] = regn[f1] = regn[t0] = 0;
-      else if (!t2to[f0]) regn[f0] = 0;   // (a type-1 read before the type-2 step)
+      if (!A.inpart(k) || A.type(k) != 1 || (k > 0 && A.inpart(k - 1) && A.type(k - 1) == 1)) continue;
+      const Sparse sp = A.sparse_of(A.run_of(k));
+      if (sp.compact) A.crows[A.slot(k)] = 10 * (int)sp.terms.size();
     }
-    for (int i = 0; i < n; i++)
-      if (t2to[i] != 1 || g_regp == 2 || !g_regp) regn[i] = 0;
+  if (part == 2) {
+    const int finp = A.to0(nst - 1);
+    for (int i = 0; i < n; i++) A.penf[i] = A.founder(i) && !A.leafp[i] && i != finp;
+    for (int k = 0; k < nst; k++) {
+      if (!A.inpart(k)) continue;
+      const int f0 = A.from0(k), f1 = A.from1(k), t0 = A.to0(k);
+      if (A.type(k) == 2) { A.penf[t0] = 0; if (!A.pristine[k]) A.penf[f0] = 0; }
+      else if (A.type(k) == 3) A.penf[f0] = A.penf[f1] = A.penf[t0] = 0;
+      else A.penf[f0] = 0;
+    }
     // persons whose first use is as the to-person of a type-2 step: their initial partial (penetrance, or prior x
     // penetrance) is formed inside that step's lanes instead of being stored and read back
     std::vector<char> seen(n, 0);
     for (int k = 0; k < nst; k++) {
-      if (!inpart(k)) continue;
-      const int ty2 = F.steps[k].x & 255, f0 = (F.steps[k].x >> 8) & 255, f1 = (F.steps[k].x >> 16) & 255, t0 = (F.steps[k].x >> 24) & 255;
-      if (ty2 == 2 && !seen[t0] && !regf[t0]) iinit[t0] = 1;
+      if (!A.inpart(k)) continue;
+      const int f0 = A.from0(k), f1 = A.from1(k), t0 = A.to0(k);
+      if (A.type(k) == 2 && !seen[t0] && !A.penf[t0]) A.iinit[t0] = 1;
       seen[f0] = 1;
-      if (ty2 != 1) seen[t0] = 1;
-      if (ty2 == 3) seen[f1] = 1;
+      if (A.type(k) != 1) seen[t0] = 1;
+      if (A.type(k) == 3) seen[f1] = 1;
     }
     for (int i = 0; i < n; i++)
-      if (leafp[i]) iinit[i] = 0;
+      if (A.leafp[i]) A.iinit[i] = 0;
   }
   // leaf offspring (parts): a non-founder whose partial is its penetrance, never changed, read by leaf steps only --
   // the steps read PEN directly (the site's penetrances stay in the slice for the task), no region, no init
-  std::vector<char> penp(n, 0);
-  if (NS == 10 && part && !g_no_penp)
-    for (int i = 0; i < n; i++) penp[i] = leafp[i] && !(F.founder[i] && i < F.nf);
-  std::vector<int> po(n);
-  std::map<int, int> mo;
+  if (part)
+    for (int i = 0; i < n; i++) A.penp[i] = A.leafp[i] && !A.founder(i);
+}
+
+// workspace layout: persons' partials, marriage partials, the type-3 products.  Parts put the leaf prefix's regions
+// first (a task's items share them)
+void layout_workspace(WaveFamily& A) {
+  const int n = A.n, nst = A.nst, NS = A.NS, part = A.part, tmp = A.tmp;
+  A.po.assign(n, 0);
   int off = 0, LSZ = 0;
   for (int L = part ? 1 : 0; L >= 0; L--) {
     for (int i = 0; i < n; i++)
-      if (!part || leafp[i] == L) {
-        po[i] = off;
-        if (!regf[i] && !regn[i] && !penp[i]) off += NS * capP[i];   // (a register- or PEN-read founder / register-only non-founder: no region)
+      if (!part || A.leafp[i] == L) {
+        A.po[i] = off;
+        if (!A.penf[i] && !A.penp[i]) off += NS * A.capP[i];   // (a PEN-read person: no region)
       }
-    for (auto& m : capM)
-      if (!part || (int)leafs.count(m.first) == L) {
-        mo[m.first] = off;
-        off += (crows.count(m.first) ? crows[m.first] : NS * NS) * m.second;
+    for (auto& m : A.capM)
+      if (!part || (int)A.leafs.count(m.first) == L) {
+        A.mo[m.first] = off;
+        off += A.mrows(m.first) * m.second;
       }
     if (L == 1) LSZ = off;
   }
-  int TB = off, NSZ = off + tmp - LSZ;
-  // Part 2 (the per-item rest, the top rest): its own regions packed by live range (g_wspack, PM_ES_WSPACK=0: in
-  // order).  A region is live from the phase of its first write to the phase of its last read; phases are counted
-  // conservatively (consecutive steps of one type share one, a type-3 step is one, the initial partials' phase is -1,
-  // the final sum the last), and a region may take the place of one whose live range ended in an earlier phase: a
-  // wave_sync lies between them.  Smaller slices -> more slices in a CU's LDS -> more waves in flight.
-  if (part == 2 && M == 1 && NS == 10 && !g_fact && g_wspack) {
+  A.LSZ = LSZ; A.TB = off; A.NSZ = off + tmp - LSZ;
+  // Part 2 (the per-item rest, the top rest): its own regions packed by live range.  A region is live from the phase
+  // of its first write to the phase of its last read; phases are counted conservatively (consecutive steps of one type
+  // share one, a type-3 step is one, the initial partials' phase is -1, the final sum the last), and a region may take
+  // the place of one whose live range ended in an earlier phase: a wave_sync lies between them.  Smaller slices ->
+  // more slices in a CU's LDS -> more waves in flight.
+  if (part == 2 && NS == 10) {
     std::vector<int> ph(nst, -2);
     int cur = -1, prevt = -1;
     for (int k = 0; k < nst; k++) {
-      if (!inpart(k)) continue;
-      const int t = F.steps[k].x & 255;
+      if (!A.inpart(k)) continue;
+      const int t = A.type(k);
       if (t != prevt || t == 3) cur++;
       prevt = t;
       ph[k] = cur;
@@ -809,22 +692,21 @@ std::string gen_wave_family(const Family& F, int chrom, int NS, bool top, const 
       r.lo = std::min(r.lo, p);
       r.hi = std::max(r.hi, p);
     };
-    auto stored = [&](int i) { return !leafp[i] && !regf[i] && !regn[i] && !penp[i]; };
-    auto msize = [&](int sl) { return (crows.count(sl) ? crows[sl] : NS * NS) * capM[sl]; };
+    auto stored = [&](int i) { return !A.leafp[i] && !A.penf[i] && !A.penp[i]; };
+    auto msize = [&](int sl) { return A.mrows(sl) * A.mcap(sl); };
     for (int i = 0; i < n; i++)
-      if (stored(i) && !iinit[i]) touch(i, NS * capP[i], -1);   // (the initial partials written up front)
+      if (stored(i) && !A.iinit[i]) touch(i, NS * A.capP[i], -1);   // (the initial partials written up front)
     for (int k = 0; k < nst; k++) {
-      if (!inpart(k)) continue;
-      const int t = F.steps[k].x & 255, f0 = (F.steps[k].x >> 8) & 255, f1 = (F.steps[k].x >> 16) & 255, t0 = (F.steps[k].x >> 24) & 255;
-      const int sl = (F.steps[k].y >> 8) & 255;
-      if (stored(f0)) touch(f0, NS * capP[f0], ph[k]);
-      if (t == 3 && stored(f1)) touch(f1, NS * capP[f1], ph[k]);
-      if (t != 1 && stored(t0)) touch(t0, NS * capP[t0], ph[k]);
-      if (sl != 255 && !leafs.count(sl)) touch(1000 + sl, msize(sl), ph[k]);
+      if (!A.inpart(k)) continue;
+      const int t = A.type(k), f0 = A.from0(k), f1 = A.from1(k), t0 = A.to0(k), sl = A.slot(k);
+      if (stored(f0)) touch(f0, NS * A.capP[f0], ph[k]);
+      if (t == 3 && stored(f1)) touch(f1, NS * A.capP[f1], ph[k]);
+      if (t != 1 && stored(t0)) touch(t0, NS * A.capP[t0], ph[k]);
+      if (sl != 255 && !A.leafs.count(sl)) touch(1000 + sl, msize(sl), ph[k]);
       if (t == 3) touch(-1, tmp, ph[k]);
     }
-    const int fin_ = (F.steps.back().x >> 24) & 255;
-    if (stored(fin_)) touch(fin_, NS * capP[fin_], cur + 1);
+    const int fin_ = A.to0(nst - 1);
+    if (stored(fin_)) touch(fin_, NS * A.capP[fin_], cur + 1);
     // first fit over a few placement orders (the first write, the size, the live-range length; ties by the others),
     // keeping the smallest footprint
     std::vector<int> ids;
@@ -873,80 +755,129 @@ std::string gen_wave_family(const Family& F, int chrom, int NS, bool top, const 
       for (auto& b : rg)
         if (a.first < b.first && a.second.hi >= b.second.lo && b.second.hi >= a.second.lo &&
             a.second.off < b.second.off + b.second.size && b.second.off < a.second.off + a.second.size) {
-          fprintf(stderr, "es_jit: workspace regions %d and %d overlap while live (%s)\n", a.first, b.first, name.c_str());
+          fprintf(stderr, "es_jit: workspace regions %d and %d overlap while live (%s)\n", a.first, b.first, A.name.c_str());
           abort();
         }
     for (auto& r : rg) {
-      if (r.first == -1) TB = r.second.off;
-      else if (r.first >= 1000) mo[r.first - 1000] = r.second.off;
-      else po[r.first] = r.second.off;
+      if (r.first == -1) A.TB = r.second.off;
+      else if (r.first >= 1000) A.mo[r.first - 1000] = r.second.off;
+      else A.po[r.first] = r.second.off;
     }
-    if (!rg.count(-1)) TB = top_;   // (no type-3 step: tmp = 1, above the rest)
-    NSZ = std::max(1, (rg.count(-1) ? top_ : top_ + tmp) - LSZ);
+    if (!rg.count(-1)) A.TB = top_;   // (no type-3 step: tmp = 1, above the rest)
+    A.NSZ = std::max(1, (rg.count(-1) ? top_ : top_ + tmp) - LSZ);
   }
-  // (the leaf prefix writes its own regions only -- and with PM_ES_FACT its P' rows in the temporaries' region)
-  *ws_doubles = part == 1 ? (g_fact && NS == 10 ? TB + tmp : LSZ) : LSZ + M * NSZ;
-  if (getenv("PM_JIT_LAYOUT")) {
-    fprintf(stderr, "layout %s NS %d part %d top %d: LSZ %d NSZ %d tmp %d ws %d |", name.c_str(), NS, part, (int)top, LSZ, NSZ, tmp, *ws_doubles);
-    for (int i = 0; i < n; i++) fprintf(stderr, " p%d:%d%s", i, (!regf[i] && !regn[i]) ? NS * capP[i] : 0, leafp[i] ? "L" : "");
-    for (auto& m : capM) fprintf(stderr, " m%d:%d", m.first, (crows.count(m.first) ? crows[m.first] : NS * NS) * m.second);
-    fprintf(stderr, " | offsets");
-    for (int i = 0; i < n; i++) fprintf(stderr, " p%d@%d", i, po[i]);
-    for (auto& m : capM) fprintf(stderr, " m%d@%d", m.first, mo[m.first]);
-    fprintf(stderr, " tb@%d\n", TB);
-  }
-  auto S = [](long v) { return std::to_string(v); };
-  const std::string nsS = S(NS), nsq = S(NS * NS), R = S((NS * NS + g_wl - 1) / g_wl), WL = S(g_wl);
-  const bool mc = part == 2 && M > 1;   // offsets of the item's own regions carry cb (several items per call)
-  auto PO = [&](int i) { return mc && !leafp[i] ? "(" + S(po[i]) + " + cb)" : S(po[i]); };
-  auto MOf = [&](int s) { return mc && !leafs.count(s) ? "(" + S(mo[s]) + " + cb)" : S(mo[s]); };
-  const std::string TBs = mc ? "(" + S(TB) + " + cb)" : S(TB);
-  // a phase with lanes over (item c, index var < N); part 2: c's genotypes (packed 8 bits per item) and offset cb
-  auto lanes = [&](int N, const std::string& var, const std::string& body) -> std::string {
-    if (!mc) return "  for (int " + var + " = lane; " + var + " < " + S(N) + "; " + var + " += " + WL + ") {\n" + body + "  }\n";
-    return "  for (int x_ = lane; x_ < " + S(M * N) + "; x_ += " + WL + ") {\n    const int c = x_ / " + S(N) + ", " + var + " = x_ - c * " +
-           S(N) + ", cb = c * " + S(NSZ) + ";\n    const int g11 = (gg11 >> (8 * c)) & 255, g12 = (gg12 >> (8 * c)) & 255, "
-           "g22 = (gg22 >> (8 * c)) & 255;\n    (void)g11; (void)g12; (void)g22; (void)cb;\n" + body + "  }\n";
-  };
-  // a phase with lanes over the pairs e: every item's work in the lane, unrolled
-  auto items = [&](const std::string& body) -> std::string {
-    if (!mc) return body;
-    return "#pragma unroll\n      for (int c = 0; c < " + S(M) + "; c++) {\n      const int cb = c * " + S(NSZ) + ";\n" + body + "      }\n";
-  };
-  std::string code = mc ? "" : "  const int g11 = gg11, g12 = gg12, g22 = gg22;\n  (void)g11; (void)g12; (void)g22;\n";
-  for (int i = 0; i < n; i++)
-    if (regf[i] && !g_pair) code += "  double fp" + std::to_string(i) + " = 0.0;\n";
+  A.ws = part == 1 ? LSZ : LSZ + A.NSZ;   // (the leaf prefix writes its own regions only)
+}
 
-  // Founders whose partial this part reads only through pristine type-2 steps (their states' prior x penetrance
-  // terms): the partial is never stored; lane x keeps the state's penetrance (fp<i>) and the terms take it by
-  // v_readlane at the term's (wave-uniform) state -- the same value the stored partial would have held
-  // InitializePartials x SetFounderPriors, one person at a time (lanes over its states)
-  for (int i = 0; i < n; i++) {
-    if ((part == 1 && !leafp[i]) || (part == 2 && leafp[i])) continue;
-    if (regf[i]) {
-      if (!g_pair) code += lanes(NS, "x", "    fp" + S(i) + " = PEN[x * " + S(n) + " + " + S(i) + "];\n");
-      continue;
+WaveFamily analyse_wave_family(const Family& F, int chrom, int NS, bool top, const std::string& name, int part, const Opts& opt) {
+  WaveFamily A{F, chrom, NS, top, part, name, F.n, (int)F.steps.size()};
+  const int n = A.n, nst = A.nst;
+  // degrees through the peel (poly_layout's rule), capacities, temporaries (type 3 only: the W(i, j) products)
+  A.d0.assign(n, 0); A.dP.assign(n, 0); A.capP.assign(n, 0);
+  std::map<int, int> dM;
+  const bool sp3_on = NS == 10 && opt.sp3;   // founder-sparse type-3 steps (see emit_type3_sparse)
+  for (int pass = (part && top) ? 0 : 1; pass < 2; pass++) {   // (pass 0: the 10-state variant's capacities)
+    const bool tp = pass == 1 && top;
+    A.sd.clear(); dM.clear();
+    for (int i = 0; i < n; i++) {
+      A.d0[i] = A.dP[i] = (tp || !A.founder(i)) ? 0 : A.fdeg(i);
+      A.capP[i] = std::max(pass ? A.capP[i] : 0, A.dP[i] + 1);
     }
-    if (regn[i] || iinit[i] || penp[i]) continue;   // (its type-2 step forms the initial partial itself / PEN)
-    const bool fo = F.founder[i] && i < F.nf;
-    const int sx = F.sex[i];
-    const bool yf = NS == 3 && Y && sx == FEMALE;
-    const int dfull = !fo ? 0 : (Y && sx == FEMALE) ? 0 : (((X || Y) && sx == MALE) || MT) ? 1 : 2;
-    const int d = d0[i];
-    std::string b = "    const int o = " + PO(i) + " + x * " + S(capP[i]) + ";\n";
+    for (int k = 0; k < nst; k++) {
+      const int type = A.type(k), from0 = A.from0(k), from1 = A.from1(k), to0 = A.to0(k), slot = A.slot(k);
+      std::vector<int>& dP = A.dP;
+      StepDeg g{0, 0, 0, 0};
+      if (type == 1) {
+        g.a = dP[from0]; g.b = A.create(k) ? 0 : dM[slot];
+        dM[slot] = g.a + g.b;
+        A.capM[slot] = std::max(A.capM[slot], dM[slot] + 1);
+      } else if (type == 2) {
+        g.a = dP[from0]; g.b = slot == 255 ? 0 : dM[slot]; g.c = dP[to0];
+        dP[to0] = g.a + g.b + g.c;
+        A.capP[to0] = std::max(A.capP[to0], dP[to0] + 1);
+      } else {
+        g.a = dP[from0]; g.b = slot == 255 ? 0 : dM[slot]; g.c = dP[from1]; g.e = dP[to0];
+        dP[to0] = g.a + g.b + g.c + g.e;
+        A.capP[to0] = std::max(A.capP[to0], dP[to0] + 1);
+        // (the W(i, j) products: a founder-sparse step keeps only its supports' pairs; pterms' sizes)
+        auto supp = [&](int f) {
+          if (!(sp3_on && A.founder(f))) return NS;
+          return top ? (A.fdeg(f) > 0 ? 1 : 3) : A.fdeg(f) == 1 ? 2 : 3;
+        };
+        A.tmp = std::max(A.tmp, supp(from0) * supp(from1) * (g.a + g.b + g.c + 1));
+      }
+      A.sd.push_back(g);
+    }
+  }
+  A.sp3.assign(nst, 0);
+  for (int k = 0; k < nst && sp3_on; k++)
+    if (A.type(k) == 3 && (A.founder(A.from0(k)) || A.founder(A.from1(k)))) A.sp3[k] = 1;
+  classify_steps(A);
+  layout_workspace(A);
+  if (opt.layout) {
+    fprintf(stderr, "layout %s NS %d part %d top %d: LSZ %d NSZ %d tmp %d ws %d |", name.c_str(), NS, part, (int)top, A.LSZ, A.NSZ, A.tmp, A.ws);
+    for (int i = 0; i < n; i++) fprintf(stderr, " p%d:%d%s", i, !A.penf[i] ? NS * A.capP[i] : 0, A.leafp[i] ? "L" : "");
+    for (auto& m : A.capM) fprintf(stderr, " m%d:%d", m.first, A.mrows(m.first) * m.second);
+    fprintf(stderr, " | offsets");
+    for (int i = 0; i < n; i++) fprintf(stderr, " p%d@%d", i, A.po[i]);
+    for (auto& m : A.capM) fprintf(stderr, " m%d@%d", m.first, A.mo[m.first]);
+    fprintf(stderr, " tb@%d\n", A.TB);
+  }
+  return A;
+}
+
+// Emission: one function per phase kind, appending to the device function's text.  Every phase ends in a wave_sync.
+
+// a phase with the family's lanes over index var < N
+std::string lanes(int N, const std::string& var, const std::string& body) {
+  return "  for (int " + var + " = lane; " + var + " < " + S(N) + "; " + var + " += " + S(kWl) + ") {\n" + body + "  }\n";
+}
+// a phase with the family's lanes over the NS x NS pairs e
+std::string pair_lanes(const WaveFamily& A, const std::string& body) {
+  return "#pragma unroll\n  for (int r = 0; r < " + S((A.NS * A.NS + kWl - 1) / kWl) + "; r++) {\n    const int e = lane + " + S(kWl) +
+         " * r;\n    if (e < " + S(A.NS * A.NS) + ") {\n" + body + "    }\n  }\n  wave_sync();\n";
+}
+// coefficient a of the product of the register polynomials x (degree dx) and y (degree dy)
+std::string conv(const std::string& x, int dx, const std::string& y, int dy, int a) {
+  std::string acc;
+  for (int c = std::max(0, a - dy); c <= std::min(a, dx); c++)
+    acc = acc.empty() ? x + "[" + S(c) + "] * " + y + "[" + S(a - c) + "]" : "fma(" + x + "[" + S(c) + "], " + y + "[" + S(a - c) + "], " + acc + ")";
+  return acc;
+}
+// T(e = i NS + j, k) of an offspring: the 10-state tables (the de novo transmission; the plain one, quirk :1391) from
+// global memory, the bi-allelic class tables in LDS
+std::string tt(const WaveFamily& A, int csex, const std::string& e, const std::string& k, bool plain) {
+  if (A.NS == 10) return plain ? "t10[(" + e + ") * 10 + " + k + "]" : "t10dn[(" + e + ") * 10 + " + k + "]";
+  const int t = A.chrom == PM_CHR_X ? (csex == MALE ? 2 : 1) : A.chrom == PM_CHR_Y ? (csex == MALE ? 3 : 5) : A.chrom == PM_CHR_MT ? 4 : 0;
+  return "tb[" + S(t * 27) + " + (" + e + ") * 3 + " + k + "]";
+}
+
+// InitializePartials x SetFounderPriors, one person at a time (lanes over its states); persons without a region
+// (penf, penp) and those whose type-2 step forms the initial partial (iinit) are skipped
+void emit_initial_partials(const WaveFamily& A, std::string& code) {
+  const int n = A.n, NS = A.NS;
+  code += "  const int g11 = gg11, g12 = gg12, g22 = gg22;\n  (void)g11; (void)g12; (void)g22;\n";
+  for (int i = 0; i < n; i++) {
+    if ((A.part == 1 && !A.leafp[i]) || (A.part == 2 && A.leafp[i])) continue;
+    if (A.penf[i] || A.iinit[i] || A.penp[i]) continue;
+    const bool fo = A.founder(i);
+    const bool yf = NS == 3 && A.chrom == PM_CHR_Y && A.F.sex[i] == FEMALE;
+    const int dfull = !fo ? 0 : A.fdeg(i);
+    const int d = A.d0[i];
+    std::string b = "    const int o = " + A.PO(i) + " + x * " + S(A.capP[i]) + ";\n";
     for (int a = 0; a <= d; a++) b += "    W[o + " + S(a) + "] = 0.0;\n";
     if (NS == 3) {
       b += "    const double pen = PEN[(x == 0 ? g11 : x == 1 ? g12 : g22) * " + S(n) + " + " + S(i) + "];\n";
       if (yf) b += "    W[o] = 1.0;\n";
       else if (!fo) b += "    W[o] = pen;\n";
-      else if (top) b += "    if (x == 0) W[o] = pen;\n";
+      else if (A.top) b += "    if (x == 0) W[o] = pen;\n";
       else if (d == 2) b += "    W[o + 2 - x] = x == 1 ? 2 * pen : pen;\n";
       else b += "    if (x != 1) W[o + (x == 0 ? 1 : 0)] = pen;\n";
     } else {
       b += "    const double pen = PEN[x * " + S(n) + " + " + S(i) + "];\n";
       b += "    const int q = x == g11 ? 0 : x == g12 ? 1 : x == g22 ? 2 : 3;\n    (void)q;\n";
       if (!fo) b += "    W[o] = pen;\n";
-      else if (top && dfull > 0) b += "    if (q == 0) W[o] = pen;\n";
+      else if (A.top && dfull > 0) b += "    if (q == 0) W[o] = pen;\n";
       else if (d == 2) b += "    if (q != 3) W[o + 2 - q] = q == 1 ? 2 * pen : pen;\n";
       else if (d == 1) b += "    if (q == 0 || q == 2) W[o + (q == 0 ? 1 : 0)] = pen;\n";
       else b += "    if (q != 3) W[o] = pen;\n";
@@ -954,593 +885,475 @@ std::string gen_wave_family(const Family& F, int chrom, int NS, bool top, const 
     code += lanes(NS, "x", b);
   }
   code += "  wave_sync();\n";
-  // T(e = i NS + j, k) of an offspring: 10-state rows of the lane's pair(s) in registers (trow, the de novo
-  // transmission), the plain transmission (quirk :1391) and the bi-allelic class tables in LDS
-  auto tt = [&](int csex, const std::string& e, const std::string& k, bool plain) -> std::string {
-    if (NS == 10) return plain ? "t10[(" + e + ") * 10 + " + k + "]" : "t10dn[(" + e + ") * 10 + " + k + "]";
-    const int t = chrom == PM_CHR_X ? (csex == MALE ? 2 : 1) : chrom == PM_CHR_Y ? (csex == MALE ? 3 : 5) : chrom == PM_CHR_MT ? 4 : 0;
-    return "tb[" + S(t * 27) + " + (" + e + ") * 3 + " + k + "]";
-  };
-  // founder-sparse type-3 steps (10 states, one item per call): a parent of the roof is a founder
-  std::vector<char> sp3(nst, 0);
-  for (int k = 0; k < nst && sp3_on; k++) {
-    const int f0 = (F.steps[k].x >> 8) & 255, f1 = (F.steps[k].x >> 16) & 255;
-    if ((F.steps[k].x & 255) == 3 && ((F.founder[f0] && f0 < F.nf) || (F.founder[f1] && f1 < F.nf))) sp3[k] = 1;
-  }
-  size_t si = 0;
-  int fin = -1;
-  double nops = 0;
-  std::vector<char> done(nst, 0);
-  double lane_slots = 0, step_ops = 0, step_eff = 1;
-  std::vector<double> eff2(nst, 0.0);   // packed type-2 runs: the run's lane occupancy (10 r of WL lanes)
-  std::vector<double> frac1(nst, 1.0);   // type-1 steps: the fraction of the 100 pairs computed (founder-sparse rows)
-  // persons whose partial the previous phase (a type-2 phase, lanes over states) left in registers: person -> (the
-  // registers' name, the first lane); a following type-1 phase takes its coefficients by v_readlane instead of
-  // wave-uniform LDS reads (the LDS pipe is what bounds this kernel)
-  std::map<int, std::pair<std::string, int>> regp;
-  for (const int2& St : F.steps) {
-    const int kstep = (int)si;
-    const StepDeg g = sd[si++];
-    fin = (St.x >> 24) & 255;
-    if ((part == 1 && !leaf[kstep]) || (part == 2 && leaf[kstep])) continue;
-    const bool emitted = done[kstep];   // (in a fused run of type-1 steps: counted here, emitted with the run's first)
-    {   // this step's FP64 operations (per item), and the lane slots they occupy (PM_JIT_LAYOUT: the static lane
-        // occupancy -- a phase over E elements on a family's WL lanes runs ceil(E / WL) passes of WL lanes; a packed
-        // run of r type-2 steps fills 10 r of the WL lanes; PM_JIT_STEPS: per step)
-      const int type = St.x & 255, slot = (St.y >> 8) & 255, create = (St.y >> 16) & 1;
-      const double ns = NS, before = nops;
-      auto occ = [&](double E, double lanes) { return E / (std::ceil(E / lanes) * lanes); };
-      double eff = 1.0;
-      if (type == 1) {
-        nops += frac1[kstep] * ns * ns * ((g.a + 1) * ns + (create ? 0 : (g.a + 1) * (g.b + 1)));
-        eff = occ(frac1[kstep] * ns * ns, g_wl);
-      } else if (type == 2) {
-        const int ds = g.a + g.b;
-        if (pristine[kstep]) nops += ns * ((double)pterms((St.x >> 8) & 255).size() * (slot == 255 ? 1 : (g.b + 1)) + (g.c + 1) * (ds + 1));
-        else nops += ns * ((slot == 255 ? (ds + 1) * ns : ns * (g.a + 1) * (g.b + 1)) + (g.c + 1) * (ds + 1));
-        eff = eff2[kstep] > 0 ? eff2[kstep] : occ(mc ? M * ns : ns, g_wl);   // (a packed run's first step: corrected below)
-      } else {
-        const int dw = g.a + g.b + g.c;
-        double np_ = ns * ns;   // (founder-sparse: the pairs of the founders' supports only)
-        if (sp3[kstep]) {
-          const int f0 = (St.x >> 8) & 255, f1 = (St.x >> 16) & 255;
-          np_ = (double)((F.founder[f0] && f0 < F.nf) ? (int)pterms(f0).size() : 10) * ((F.founder[f1] && f1 < F.nf) ? (int)pterms(f1).size() : 10);
-        }
-        const double o1 = np_ * (g.a + 1) * (g.b + 1) * (g.c + 1) * (slot == 255 ? 1 : 2), o2 = ns * (np_ * (dw + 1) + (g.e + 1) * (dw + 1));
-        nops += o1 + o2;
-        eff = (o1 + o2) / (o1 / occ(np_, g_wl) + o2 / occ(mc ? M * ns : ns, g_wl));
-      }
-      lane_slots += (nops - before) / eff;
-      step_ops = nops - before;
-      step_eff = eff;
-      if (getenv("PM_JIT_STEPS"))
-        fprintf(stderr, "  step %s part %d M %d k %d type %d ops %.0f eff %.3f\n", name.c_str(), part, M, kstep, type, step_ops, eff);
-    }
-    const int type = St.x & 255, from0 = (St.x >> 8) & 255, from1 = (St.x >> 16) & 255, to0 = (St.x >> 24) & 255;
-    const int slot = (St.y >> 8) & 255, create = (St.y >> 16) & 1, fa2mo = (St.y >> 17) & 1;
-    if (emitted) continue;
-    if (type == 1) {   // lanes over the pairs e: S(e) = sum_k T(e, k) P_off[k] in registers, then M(e) *= S(e) in place
-      const int off_ = from0, csex = F.sex[off_], pcap = capP[off_], mcap = capM[slot];
-      std::string b = "      double s[" + S(g.a + 1) + "];\n";
-      for (int a = 0; a <= g.a; a++) {
-        b += "      s[" + S(a) + "] = 0.0;\n";
-        b += "#pragma unroll\n      for (int k = 0; k < " + nsS + "; k++) s[" + S(a) + "] = fma(" +
-             (NS == 10 ? std::string(g_tr_regs ? "(r == 0 ? tr0[k] : tr1[k])" : "t10dn[e * 10 + k]") : tt(csex, "e", "k", false)) + ", " +
-             (penp[off_] ? "PEN[k * " + S(n) + " + " + S(off_) + "]" : "W[" + PO(off_) + " + k * " + S(pcap) + " + " + S(a) + "]") + ", s[" + S(a) + "]);\n";
-      }
-      const std::string me = MOf(slot) + " + e * " + S(mcap);
-      if (create) {
-        for (int a = 0; a <= g.a; a++) b += "      W[" + me + " + " + S(a) + "] = s[" + S(a) + "];\n";
-      } else {
-        b += "      double m[" + S(g.b + 1) + "];\n";
-        for (int c = 0; c <= g.b; c++) b += "      m[" + S(c) + "] = W[" + me + " + " + S(c) + "];\n";
-        for (int a = 0; a <= g.a + g.b; a++) {
-          std::string acc;
-          for (int c = std::max(0, a - g.a); c <= std::min(a, g.b); c++)
-            acc = acc.empty() ? "m[" + S(c) + "] * s[" + S(a - c) + "]" : "fma(m[" + S(c) + "], s[" + S(a - c) + "], " + acc + ")";
-          b += "      W[" + me + " + " + S(a) + "] = " + acc + ";\n";
-        }
-      }
-      if (NS == 10 && !mc) {
-        // a run of consecutive type-1 steps (this part's; they only read offspring partials and their own marriage
-        // partial) is one phase: lanes over both pairs (lane, lane + 64 < 100), one pass over k for every step of
-        // the run (each offspring coefficient read from LDS once for the two pairs: wave-uniform broadcasts), then per
-        // marriage partial the steps' products chained in registers and one write -- the same operations in the
-        // same order as step by step
-        const std::vector<int> run = run_of(kstep);
-        for (int k2 : run) done[k2] = 1;
-        std::vector<int> slots;   // the marriage partials the run writes, in order of first use
-        for (int k2 : run) {
-          const int sl2 = (F.steps[k2].y >> 8) & 255;
-          if (std::find(slots.begin(), slots.end(), sl2) == slots.end()) slots.push_back(sl2);
-        }
-        const Sparse spi = sparse_of(run);
-        const std::vector<std::pair<int, int>>& sp_terms = spi.terms;
-        const bool sp_father = spi.father;
-        const bool sparse = !sp_terms.empty();
-        if (sparse) {   // (the run's first step was counted at 100 pairs above)
-          const double fr = 10.0 * sp_terms.size() / 100.0;
-          nops -= (1.0 - fr) * 100.0 * ((g.a + 1) * 10.0 + (create ? 0 : (g.a + 1) * (g.b + 1)));
-          for (int k2 : run) frac1[k2] = fr;
-        }
-        const int nsp = 10 * (int)sp_terms.size();   // (sparse: the rows, passes of g_wl lanes over them)
-        const int npair = sparse ? (nsp + g_wl - 1) / g_wl : (100 + g_wl - 1) / g_wl;
-        bool fact = g_fact && !sparse;
-        for (int k2 : run)
-          if (regp.count((F.steps[k2].x >> 8) & 255)) fact = false;
-        std::vector<int> pfo(run.size(), 0);   // PM_ES_FACT: each step's P' rows at TB + pfo[q]
-        if (fact) {   // P'(m, a) = sum_k M(m, k) P(k, a); M's row m is T10dn's row of the parent pair (x x, y y), m = {x, y}
-          int at = 0;
-          for (size_t q = 0; q < run.size(); q++) {
-            const int offq = (F.steps[run[q]].x >> 8) & 255, ga = sd[run[q]].a, na = ga + 1;
-            pfo[q] = at;
-            const std::string P = penp[offq] ? "PEN[k * " + S(n) + " + " + S(offq) + "]"
-                                             : "W[" + PO(offq) + " + k * " + S(capP[offq]) + " + a]";
-            code += lanes(10 * na, "x", "    const int m = x / " + S(na) + ", a = x - m * " + S(na) + ";\n    (void)a;\n"
-                          "    const double* Mr = t10dn + kMrow[m] * 10;\n    double s = 0.0;\n#pragma unroll\n"
-                          "    for (int k = 0; k < 10; k++) s = fma(Mr[k], " + P + ", s);\n    W[" + TBs + " + " + S(at) + " + x] = s;\n");
-            at += 10 * na;
-          }
-          code += "  wave_sync();\n";
-        }
-        std::string c1 = "  {\n";
-        if (sparse) {   // pass pr: row p = lane + pr g_wl (state o of the spouse, term qi of the founder's support); rows past
-                        // the support compute an in-range pair and store nothing
-          const std::string gq[3] = {"g11", "g12", "g22"};
-          for (int pr = 0; pr < npair; pr++) {
-            const std::string P = S(pr), qi = "qi" + P;
-            std::string sF = gq[sp_terms.back().first];
-            for (int q = (int)sp_terms.size() - 2; q >= 0; q--) sF = qi + " == " + S(q) + " ? " + gq[sp_terms[q].first] + " : " + sF;
-            c1 += "    const int p" + P + " = lane + " + S(pr * g_wl) + ", " + qi + " = p" + P + " / 10, o" + P + " = p" + P + " - " + qi +
-                  " * 10, sF" + P + " = " + sF + ";\n    const int e" + P + " = " +
-                  (sp_father ? "sF" + P + " * 10 + o" + P : "o" + P + " * 10 + sF" + P) + ";\n";
-          }
-        } else
-          for (int pr = 1; pr < npair; pr++)
-            c1 += "    const int e" + S(pr) + " = lane + " + S(pr * g_wl) + ", e" + S(pr) + "c = e" + S(pr) + " < 100 ? e" + S(pr) + " : lane;\n";
-        for (size_t q = 0; q < run.size(); q++) {
-          const int ga = sd[run[q]].a;
-          for (int pr = 0; pr < npair; pr++) {
-            c1 += "    double s" + S(pr) + "_" + S(q) + "[" + S(ga + 1) + "];\n";
-            for (int a = 0; a <= ga; a++) c1 += "    s" + S(pr) + "_" + S(q) + "[" + S(a) + "] = 0.0;\n";
-          }
-        }
-        if (fact) {   // per pair: 0.25 x the P' values at its four Mendelian children (packed bytes, kMend)
-          for (int pr = 0; pr < npair; pr++)
-            c1 += "    const unsigned cm" + S(pr) + " = kMend[" + (pr ? "e" + S(pr) + "c" : std::string("lane")) + "];\n";
-          for (size_t q = 0; q < run.size(); q++) {
-            const int ga = sd[run[q]].a, na = ga + 1;
-            for (int pr = 0; pr < npair; pr++)
-              for (int a = 0; a <= ga; a++) {
-                auto pf = [&](int t) { return "W[" + TBs + " + " + S(pfo[q] + a) + " + " + S(na) + " * ((cm" + S(pr) + " >> " + S(8 * t) + ") & 255)]"; };
-                c1 += "    s" + S(pr) + "_" + S(q) + "[" + S(a) + "] = 0.25 * (((" + pf(0) + " + " + pf(1) + ") + " + pf(2) + ") + " + pf(3) + ");\n";
-              }
-          }
-        }
-        // (k unrolled by 2 only: fully unrolled, the scheduler hoists every offspring coefficient's LDS read and
-        // spills)
-        if (!fact) {
-        c1 += "#pragma unroll 2\n    for (int k = 0; k < 10; k++) {\n";
-        if (sparse) {
-          c1 += "      const double t0 = t10dn[e0 * 10 + k]";
-          for (int pr = 1; pr < npair; pr++) c1 += ", t" + S(pr) + " = t10dn[e" + S(pr) + " * 10 + k]";
-          c1 += ";\n";
-        }
-        else if (npair > 2) {   // (pair mode: the rows of this lane's four pairs)
-          c1 += "      const double t0 = t10dn[lane * 10 + k]";
-          for (int pr = 1; pr < npair; pr++) c1 += ", t" + S(pr) + " = t10dn[e" + S(pr) + "c * 10 + k]";
-          c1 += ";\n";
-        } else
-          c1 += g_expt == 1 ? "      const double t0 = 0.001 * k, t1 = 0.002 * k;\n"   // (timing experiment only: wrong values)
-                : g_tr_regs ? "      const double t0 = tr0[k], t1 = tr1[k];\n"
-                            : "      const double t0 = t10dn[lane * 10 + k], t1 = t10dn[e1c * 10 + k];\n";
-        for (size_t q = 0; q < run.size(); q++) {
-          const int2 Sq = F.steps[run[q]];
-          const int offq = (Sq.x >> 8) & 255, ga = sd[run[q]].a;
-          for (int a = 0; a <= ga; a++) {
-            if (regp.count(offq) && (g_regp != 2 || q % 2 == 1)) {   // from the lanes of the type-2 phase that computed it
-              const std::string v = regp[offq].first + S(a), L = S(regp[offq].second) + " + k";
-              c1 += "      {\n        const double p = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(" + v + "), " + L +
-                    "), __builtin_amdgcn_readlane(__double2loint(" + v + "), " + L + "));\n";
-            } else
-            c1 += g_expt == 2 ? "      {\n        const double p = 0.5 + 0.01 * k + " + S(a) + ";\n"   // (timing experiment only)
-                              : penp[offq] ? "      {\n        const double p = PEN[k * " + S(n) + " + " + S(offq) + "];\n"
-                              : "      {\n        const double p = W[" + PO(offq) + " + k * " + S(capP[offq]) + " + " + S(a) + "];\n";
-            for (int pr = 0; pr < npair; pr++)
-              c1 += "        s" + S(pr) + "_" + S(q) + "[" + S(a) + "] = fma(t" + S(pr) + ", p, s" + S(pr) + "_" + S(q) + "[" + S(a) + "]);\n";
-            c1 += "      }\n";
-          }
-        }
-        c1 += "    }\n";
-        }
-        // per pair: each marriage partial chained through its steps in registers, one write
-        for (int pr = 0; pr < npair; pr++) {
-          const std::string sp = "s" + S(pr) + "_", e = spi.compact ? "p" + S(pr) : sparse ? "e" + S(pr) : pr ? "e" + S(pr) : "lane";
-          c1 += sparse ? "    if (p" + S(pr) + " < " + S(nsp) + ") {\n" : pr ? "    if (e" + S(pr) + " < 100) {\n" : "    {\n";
-          int cid = 0;
-          for (int sl2 : slots) {
-            const std::string mev = MOf(sl2) + " + " + e + " * " + S(capM[sl2]);
-            std::string cur;   // the register array holding the slot's current coefficients
-            int dcur = -1;
-            for (size_t q = 0; q < run.size(); q++) {
-              const int2 Sq = F.steps[run[q]];
-              if (((Sq.y >> 8) & 255) != sl2) continue;
-              const int ga = sd[run[q]].a, gb = sd[run[q]].b, cr = (Sq.y >> 16) & 1;
-              const std::string sq = sp + S(q);
-              if (cr) { cur = sq; dcur = ga; continue; }
-              if (dcur < 0) {   // the slot's coefficients so far, from LDS
-                cur = "m" + S(pr) + "_" + S(cid++);
-                c1 += "      double " + cur + "[" + S(gb + 1) + "];\n";
-                for (int c = 0; c <= gb; c++) c1 += "      " + cur + "[" + S(c) + "] = W[" + mev + " + " + S(c) + "];\n";
-                dcur = gb;
-              }
-              const std::string nx = "m" + S(pr) + "_" + S(cid++);
-              c1 += "      double " + nx + "[" + S(ga + gb + 1) + "];\n";
-              for (int a = 0; a <= ga + gb; a++) {
-                std::string acc;
-                for (int c = std::max(0, a - ga); c <= std::min(a, gb); c++)
-                  acc = acc.empty() ? cur + "[" + S(c) + "] * " + sq + "[" + S(a - c) + "]"
-                                    : "fma(" + cur + "[" + S(c) + "], " + sq + "[" + S(a - c) + "], " + acc + ")";
-                c1 += "      " + nx + "[" + S(a) + "] = " + acc + ";\n";
-              }
-              cur = nx;
-              dcur = ga + gb;
-            }
-            for (int a = 0; a <= dcur; a++) c1 += "      W[" + mev + " + " + S(a) + "] = " + cur + "[" + S(a) + "];\n";
-          }
-          c1 += "    }\n";
-        }
-        c1 += "  }\n  wave_sync();\n";
-        code += c1;
-      } else
-      code += "#pragma unroll\n  for (int r = 0; r < " + R + "; r++) {\n    const int e = lane + " + WL + " * r;\n    if (e < " + nsq + ") {\n" + items(b) +
-              "    }\n  }\n  wave_sync();\n";
-    } else if (type == 2) {   // lanes over i: S(i) = sum_j P_from[j] M(j, i) in registers, then P_to[i] *= S(i) in place
-      const int sf = from0, stt = to0, fcap = capP[sf], tcap = capP[stt];
-      const int ds = g.a + g.b;
-      // independent type-2 steps of one shape that follow this one (this part's): one phase, 16 lanes per step, the
-      // lane's step selecting its partials' offsets
-      std::vector<int> run{kstep};
-      if (NS == 10 && !mc && g_pack) {
-        auto sig2 = [&](int k2) {
-          const int2 Q = F.steps[k2];
-          const int f2 = (Q.x >> 8) & 255, t2 = (Q.x >> 24) & 255, s2 = (Q.y >> 8) & 255;
-          return std::vector<int>{pristine[k2], sd[k2].a, sd[k2].b, sd[k2].c, s2 == 255, capP[f2], capP[t2], s2 == 255 ? 0 : capM[s2],
-                                  d0[f2], (int)crows.count(s2), (int)regf[f2], (int)regn[t2], (int)iinit[t2], F.founder[t2] && t2 < F.nf,
-                                  (F.founder[t2] && t2 < F.nf) ? ((Y && F.sex[t2] == FEMALE) ? 0 : (((X || Y) && F.sex[t2] == MALE) || MT) ? 1 : 2)
-                                                               : -1};
-        };
-        const std::vector<int> sg0 = sig2(kstep);
-        for (int k2 = kstep + 1; k2 < nst && (int)run.size() < g_wl / 16; k2++) {
-          if ((part == 1 && !leaf[k2]) || (part == 2 && leaf[k2])) continue;
-          const int2 Q = F.steps[k2];
-          if ((Q.x & 255) != 2 || sig2(k2) != sg0) break;
-          const int f2 = (Q.x >> 8) & 255, t2 = (Q.x >> 24) & 255;
-          bool indep = true;
-          for (int k3 : run) {
-            const int f3 = (F.steps[k3].x >> 8) & 255, t3 = (F.steps[k3].x >> 24) & 255;
-            if (t2 == t3 || f2 == t3 || f3 == t2) indep = false;
-          }
-          if (!indep) break;
-          run.push_back(k2);
-        }
-      }
-      if (run.size() > 1) {
-        for (int k2 : run) eff2[k2] = (double)NS * run.size() / g_wl;
-        lane_slots += step_ops / eff2[kstep] - step_ops / step_eff;
-      }
-      std::string OF = PO(sf), OT = PO(stt), OM = slot == 255 ? "" : MOf(slot), pre;
-      if (run.size() > 1) {
-        auto sel = [&](const std::function<std::string(int)>& f) {
-          std::string e = f(run.back());
-          for (int q = (int)run.size() - 2; q >= 0; q--) e = "q_ == " + S(q) + " ? " + f(run[q]) + " : " + e;
-          return e;
-        };
-        pre = "      const int of_ = " + sel([&](int k2) { return PO((F.steps[k2].x >> 8) & 255); }) +
-              ";\n      const int ot_ = " + sel([&](int k2) { return PO((F.steps[k2].x >> 24) & 255); }) + ";\n";
-        if (slot != 255) {   // (and the marriage partial's orientation: M(i, j) or M(j, i))
-          pre += "      const int om_ = " + sel([&](int k2) { return MOf((F.steps[k2].y >> 8) & 255); }) + ";\n";
-          pre += "      const int si_ = " + sel([&](int k2) { return std::string((F.steps[k2].y >> 17) & 1 ? "1" : nsS); }) + ", sj_ = " +
-                 sel([&](int k2) { return std::string((F.steps[k2].y >> 17) & 1 ? nsS : "1"); }) + ";\n";
-        }
-        OF = "of_"; OT = "ot_"; OM = "om_";
-        for (int k2 : run) done[k2] = 1;
-      }
+}
 
-      std::string b = "    double s[" + S(ds + 1) + "];\n";
-      for (int a = 0; a <= ds; a++) b += "    s[" + S(a) + "] = 0.0;\n";
-      if (pristine[kstep]) {
-        // the founder's partial is prior x penetrance: state g11 / g12 / g22 holds one monomial, at coefficient
-        // 2 - q (degree 2: q = 0, 1, 2), 1 / - / 0 (degree 1: no geno12) or 0 (degree 0); the other states are zero.
-        // The sum visits j in the dense loop's order and skips the zero terms (fma(0, g, s) == s), so it is
-        // bit-identical to the dense sum (q in the dense loop's coefficient order u = 0, 1, 2 at one j, should two of
-        // the genotypes coincide)
-        // No loop over j: the terms' states are wave-uniform, so their order by j (stable: ties keep the coefficient
-        // order) is one of at most 6, chosen once by a uniform switch; each case adds the terms in that order
-        const std::string gq[3] = {"g11", "g12", "g22"};
-        const std::vector<std::pair<int, int>> tm = pterms(sf);
-        auto term = [&](int q, int u, int qpos) {
-          std::string t = "      {\n        const int j = " + gq[q] + ";\n";
-          if (regf[sf]) {   // the founder's penetrance at state j from lane j (x 2 for the heterozygote's coefficient)
-            auto pj = [&](int fperson) {
-              const std::string v = "fp" + S(fperson);
-              return "__hiloint2double(__builtin_amdgcn_readlane(__double2hiint(" + v + "), j), __builtin_amdgcn_readlane(__double2loint(" +
-                     v + "), j))";
-            };
-            std::string pe;
-            if (g_pair) {   // the penetrance the init phase would have stored, from PEN (one read: the person index selected)
-              std::string who = S((F.steps[run.back()].x >> 8) & 255);
-              for (int r2 = (int)run.size() - 2; r2 >= 0; r2--) who = "q_ == " + S(r2) + " ? " + S((F.steps[run[r2]].x >> 8) & 255) + " : " + who;
-              pe = "PEN[j * " + S(n) + " + (" + who + ")]";
-            } else {
-              pe = pj((F.steps[run.back()].x >> 8) & 255);
-              for (int r2 = (int)run.size() - 2; r2 >= 0; r2--) pe = "q_ == " + S(r2) + " ? " + pj((F.steps[run[r2]].x >> 8) & 255) + " : " + pe;
-            }
-            t += "        const double pj_ = " + pe + ";\n";
-            t += (!top && d0[sf] == 2 && q == 1) ? "        const double f = 2 * pj_;\n" : "        const double f = pj_;\n";
-          } else t += "        const double f = W[" + OF + " + j * " + S(fcap) + " + " + S(u) + "];\n";
-          if (slot == 255) t += "        s[" + S(u) + "] += f;\n";
-          else {
-            const int mcap = capM[slot];
-            const std::string me = crows.count(slot) ? "(" + S(qpos * 10) + " + i)"   // (compact rows)
-                                 : run.size() > 1 ? "(i * si_ + j * sj_)" : fa2mo ? "(j * " + nsS + " + i)" : "(i * " + nsS + " + j)";
-            for (int v = 0; v <= g.b; v++)
-              t += "        s[" + S(u + v) + "] = fma(f, W[" + OM + " + " + me + " * " + S(mcap) + " + " + S(v) + "], s[" + S(u + v) + "]);\n";
-          }
-          return t + "      }\n";
-        };
-        const int nt = (int)tm.size();
-        if (nt == 1) b += term(tm[0].first, tm[0].second, 0);
-        else {
-          // bit c of the case: term a (of pair c) is not after term b, in the terms' order a < b
-          std::vector<std::pair<int, int>> prs;
-          for (int a = 0; a < nt; a++)
-            for (int c = a + 1; c < nt; c++) prs.push_back({a, c});
-          std::string key;
-          for (size_t c = 0; c < prs.size(); c++)
-            key += std::string(c ? " | " : "") + "((" + gq[tm[prs[c].first].first] + " <= " + gq[tm[prs[c].second].first] + ") << " + S(c) + ")";
-          b += "    switch (" + key + ") {\n";
-          for (int cs = 0; cs < (1 << prs.size()); cs++) {
-            std::vector<int> ord(nt);
-            for (int a = 0; a < nt; a++) ord[a] = a;
-            auto before = [&](int x, int y) {   // x before y in this case
-              for (size_t c = 0; c < prs.size(); c++) {
-                if (prs[c].first == x && prs[c].second == y) return ((cs >> c) & 1) != 0;
-                if (prs[c].first == y && prs[c].second == x) return ((cs >> c) & 1) == 0;
-              }
-              return x < y;
-            };
-            std::stable_sort(ord.begin(), ord.end(), before);
-            b += "      case " + S(cs) + ":\n";
-            for (int a : ord) b += term(tm[a].first, tm[a].second, a);
-            b += "      break;\n";
-          }
-          b += "    }\n";
-        }
-      } else if (slot == 255) {
-        for (int a = 0; a <= ds; a++)
-          b += "#pragma unroll\n    for (int j = 0; j < " + nsS + "; j++) s[" + S(a) + "] += W[" + OF + " + j * " + S(fcap) + " + " +
-               S(a) + "];\n";
-      } else {
-        const int mcap = capM[slot];
-        const std::string me = run.size() > 1 ? "(i * si_ + j * sj_)" : fa2mo ? "(j * " + nsS + " + i)" : "(i * " + nsS + " + j)";
-        b += std::string(run.size() > 1 ? "#pragma unroll 2" : "#pragma unroll") + "\n    for (int j = 0; j < " + nsS + "; j++) {\n";
-        for (int u = 0; u <= g.a; u++) b += "      const double f" + S(u) + " = W[" + OF + " + j * " + S(fcap) + " + " + S(u) + "];\n";
-        for (int v = 0; v <= g.b; v++) b += "      const double g" + S(v) + " = W[" + OM + " + " + me + " * " + S(mcap) + " + " + S(v) + "];\n";
-        for (int u = 0; u <= g.a; u++)
-          for (int v = 0; v <= g.b; v++) b += "      s[" + S(u + v) + "] = fma(f" + S(u) + ", g" + S(v) + ", s[" + S(u + v) + "]);\n";
-        b += "    }\n";
-      }
-      const bool keep = NS == 10 && !mc && g_regp;   // (the outputs stay in registers for a following type-1 phase)
-      const bool rn = keep && regn[stt];   // (the to-person is register-only: its partial was its penetrance)
-      b += "    double t[" + S(g.c + 1) + "];\n";
-      if ((keep || (NS == 10 && !mc && g_pair)) && iinit[stt]) {   // the initial partial at state i (InitializePartials x SetFounderPriors)
-        std::string tp = S((F.steps[run.back()].x >> 24) & 255);   // (packed: the lane group's to-person)
-        for (int r2 = (int)run.size() - 2; r2 >= 0; r2--) tp = "q_ == " + S(r2) + " ? " + S((F.steps[run[r2]].x >> 24) & 255) + " : " + tp;
-        const bool fo2 = F.founder[stt] && stt < F.nf;
-        const int sx2 = F.sex[stt];
-        const int dfull2 = !fo2 ? 0 : (Y && sx2 == FEMALE) ? 0 : (((X || Y) && sx2 == MALE) || MT) ? 1 : 2;
-        const int d2 = d0[stt];
-        b += "    const double pen_ = PEN[i * " + S(n) + " + (" + tp + ")];\n";
-        b += "    const int qi_ = i == g11 ? 0 : i == g12 ? 1 : i == g22 ? 2 : 3;\n    (void)qi_;\n";
-        for (int c = 0; c <= g.c; c++) {
-          std::string v = "0.0";
-          if (!fo2) v = c == 0 ? "pen_" : "0.0";
-          else if (top && dfull2 > 0) v = c == 0 ? "(qi_ == 0 ? pen_ : 0.0)" : "0.0";
-          else if (d2 == 2) v = c == 0 ? "(qi_ == 2 ? pen_ : 0.0)" : c == 1 ? "(qi_ == 1 ? 2 * pen_ : 0.0)" : c == 2 ? "(qi_ == 0 ? pen_ : 0.0)" : "0.0";
-          else if (d2 == 1) v = c == 0 ? "(qi_ == 2 ? pen_ : 0.0)" : c == 1 ? "(qi_ == 0 ? pen_ : 0.0)" : "0.0";
-          else v = c == 0 ? "(qi_ != 3 ? pen_ : 0.0)" : "0.0";
-          b += "    t[" + S(c) + "] = " + v + ";\n";
-        }
-      } else
-        for (int c = 0; c <= g.c; c++) b += "    t[" + S(c) + "] = W[" + OT + " + i * " + S(tcap) + " + " + S(c) + "];\n";
-      const std::string xr = "xr" + S(kstep) + "_";
-      if (keep)
-        for (int a = 0; a <= g.c + ds; a++) code += "  double " + xr + S(a) + " = 0.0;\n";
-      for (int a = 0; a <= g.c + ds; a++) {
-        std::string acc;
-        for (int c = std::max(0, a - ds); c <= std::min(a, g.c); c++)
-          acc = acc.empty() ? "t[" + S(c) + "] * s[" + S(a - c) + "]" : "fma(t[" + S(c) + "], s[" + S(a - c) + "], " + acc + ")";
-        if (rn) b += "    " + xr + S(a) + " = " + acc + ";\n";
-        else if (keep) b += "    " + xr + S(a) + " = " + acc + ";\n    W[" + OT + " + i * " + S(tcap) + " + " + S(a) + "] = " + xr + S(a) + ";\n";
-        else b += "    W[" + OT + " + i * " + S(tcap) + " + " + S(a) + "] = " + acc + ";\n";
-      }
-      for (size_t q = 0; q < run.size(); q++) regp.erase((F.steps[run[q]].x >> 24) & 255);
-      if (keep)
-        for (size_t q = 0; q < run.size(); q++) regp[(F.steps[run[q]].x >> 24) & 255] = {xr, run.size() > 1 ? 16 * (int)q : 0};
-      if (run.size() > 1)
-        code += "  {\n    const int q_ = lane >> 4, i = lane & 15;\n    if (q_ < " + S(run.size()) + " && i < " + nsS + ") {\n" + pre + b +
-                "    }\n  }\n  wave_sync();\n";
-      else code += lanes(NS, "i", b) + "  wave_sync();\n";
-    } else if (sp3[kstep]) {
-      // founder-sparse type-3 step (10 states): a founder's partial is prior x penetrance times whatever multiplied into
-      // it -- zero outside the 1-3 states of its prior (the site's g11, g12, g22; pterms) -- so W(e) = P_fa[i] M(e) P_mo[j]
-      // is zero off those pairs, and so is every term T(e, k) W(e) they would add (+0: the sums keep their bits).  Only
-      // the nI x nJ pairs (i, j) in ascending e are formed (lanes over them) and summed (in the same ascending e order),
-      // instead of all 100.  The states of a founder's support are sorted at run time (wave-uniform).
-      regp.erase(to0);
-      const int fa = from0, mo_ = from1, off_ = to0, csex = F.sex[off_];
-      const int dw = g.a + g.b + g.c, ww = dw + 1;
-      auto support = [&](int f, const std::string& pre) -> std::pair<int, std::string> {
-        if (!(F.founder[f] && f < F.nf)) return {10, ""};
-        const auto t = pterms(f);
-        std::string c;
-        for (size_t q = 0; q < t.size(); q++)
-          c += "  int " + pre + S(q) + " = " + (t[q].first == 0 ? "g11" : t[q].first == 1 ? "g12" : "g22") + ";\n";
-        auto sw = [&](int a, int b2) {
-          return "  if (" + pre + S(a) + " > " + pre + S(b2) + ") { const int x_ = " + pre + S(a) + "; " + pre + S(a) + " = " + pre + S(b2) +
-                 "; " + pre + S(b2) + " = x_; }\n";
-        };
-        if (t.size() >= 2) c += sw(0, 1);
-        if (t.size() == 3) c += sw(1, 2) + sw(0, 1);
-        return {(int)t.size(), c};
-      };
-      const std::string pI = "sI" + S(kstep) + "_", pJ = "sJ" + S(kstep) + "_";
-      const auto sI = support(fa, pI), sJ = support(mo_, pJ);
-      const int nI = sI.first, nJ = sJ.first, NP = nI * nJ;
-      auto pick = [&](const std::string& pre, int nn, const std::string& idx) {   // the idx-th state of a support
-        if (nn == 10) return idx;
-        std::string r = pre + S(nn - 1);
-        for (int q = nn - 2; q >= 0; q--) r = "(" + idx + " == " + S(q) + " ? " + pre + S(q) + " : " + r + ")";
-        return r;
-      };
-      code += sI.second + sJ.second;
-      std::string b = "      const int ia = p / " + S(nJ) + ", jb = p - ia * " + S(nJ) + ";\n      const int i = " + pick(pI, nI, "ia") +
-                      ", j = " + pick(pJ, nJ, "jb") + ", e = i * " + nsS + " + j;\n      double w[" + S(ww) + "];\n";
-      for (int a = 0; a <= dw; a++) b += "      w[" + S(a) + "] = 0.0;\n";
-      for (int u = 0; u <= g.a; u++)
-        for (int v = 0; v <= g.b; v++)
-          for (int c = 0; c <= g.c; c++) {
-            const std::string m = slot == 255 ? "" : " * W[" + MOf(slot) + " + e * " + S(capM[slot]) + " + " + S(v) + "]";
-            b += "      w[" + S(u + v + c) + "] = fma(W[" + PO(fa) + " + i * " + S(capP[fa]) + " + " + S(u) + "]" + m + ", W[" +
-                 PO(mo_) + " + j * " + S(capP[mo_]) + " + " + S(c) + "], w[" + S(u + v + c) + "]);\n";
-          }
-      for (int a = 0; a <= dw; a++) b += "      W[" + TBs + " + p * " + S(ww) + " + " + S(a) + "] = w[" + S(a) + "];\n";
-      code += "#pragma unroll\n  for (int r = 0; r < " + S((NP + g_wl - 1) / g_wl) + "; r++) {\n    const int p = lane + " + WL + " * r;\n    if (p < " +
-              S(NP) + ") {\n" + b + "    }\n  }\n  wave_sync();\n";
-      std::string b2 = "    double s[" + S(ww) + "];\n";
-      for (int a = 0; a <= dw; a++) b2 += "    s[" + S(a) + "] = 0.0;\n";
-      b2 += "    for (int p = 0; p < " + S(NP) + "; p++) {\n      const int ia = p / " + S(nJ) + ", jb = p - ia * " + S(nJ) + ";\n      const int e = " +
-            pick(pI, nI, "ia") + " * " + nsS + " + " + pick(pJ, nJ, "jb") + ";\n      const double t = " + tt(csex, "e", "k", slot != 255) + ";\n";
-      for (int a = 0; a <= dw; a++) b2 += "      s[" + S(a) + "] = fma(t, W[" + TBs + " + p * " + S(ww) + " + " + S(a) + "], s[" + S(a) + "]);\n";
-      b2 += "    }\n    double t[" + S(g.e + 1) + "];\n";
-      for (int c = 0; c <= g.e; c++) b2 += "    t[" + S(c) + "] = W[" + PO(off_) + " + k * " + S(capP[off_]) + " + " + S(c) + "];\n";
-      for (int a = 0; a <= g.e + dw; a++) {
-        std::string acc;
-        for (int c = std::max(0, a - dw); c <= std::min(a, g.e); c++)
-          acc = acc.empty() ? "t[" + S(c) + "] * s[" + S(a - c) + "]" : "fma(t[" + S(c) + "], s[" + S(a - c) + "], " + acc + ")";
-        b2 += "    W[" + PO(off_) + " + k * " + S(capP[off_]) + " + " + S(a) + "] = " + acc + ";\n";
-      }
-      code += lanes(NS, "k", b2) + "  wave_sync();\n";
-    } else {   // W(e) = P_fa[i] M(e) P_mo[j] -> LDS; lanes over k: S(k) = sum_e T(e, k) W(e), P_off[k] *= S(k) in place
-      regp.erase(to0);
-      const int fa = from0, mo_ = from1, off_ = to0, csex = F.sex[off_];
-      const int dw = g.a + g.b + g.c, ww = dw + 1;
-      std::string b = "      const int i = e / " + nsS + ", j = e - i * " + nsS + ";\n      double w[" + S(ww) + "];\n";
-      for (int a = 0; a <= dw; a++) b += "      w[" + S(a) + "] = 0.0;\n";
-      for (int u = 0; u <= g.a; u++)
-        for (int v = 0; v <= g.b; v++)
-          for (int c = 0; c <= g.c; c++) {
-            const std::string m = slot == 255 ? "" : " * W[" + MOf(slot) + " + e * " + S(capM[slot]) + " + " + S(v) + "]";
-            b += "      w[" + S(u + v + c) + "] = fma(W[" + PO(fa) + " + i * " + S(capP[fa]) + " + " + S(u) + "]" + m + ", W[" +
-                 PO(mo_) + " + j * " + S(capP[mo_]) + " + " + S(c) + "], w[" + S(u + v + c) + "]);\n";
-          }
-      for (int a = 0; a <= dw; a++) b += "      W[" + TBs + " + e * " + S(ww) + " + " + S(a) + "] = w[" + S(a) + "];\n";
-      code += "#pragma unroll\n  for (int r = 0; r < " + R + "; r++) {\n    const int e = lane + " + WL + " * r;\n    if (e < " + nsq + ") {\n" + items(b) +
-              "    }\n  }\n  wave_sync();\n";
-      std::string b2 = "    double s[" + S(ww) + "];\n";
-      for (int a = 0; a <= dw; a++) b2 += "    s[" + S(a) + "] = 0.0;\n";
-      if (NS == 10 && slot != 255 && !g_no_t3z) {
-        // the plain transmission (:1391) is the Mendelian table: 16-31 of a child state's 100 parent pairs are non-zero
-        // (1, 1/2 or 1/4).  Each lane k runs over its non-zero pairs only, in ascending e (the LDS list t3z, e << 2 |
-        // value code): the pairs skipped would add +0 (T = 0, W finite and >= 0), so every sum keeps its bits -- and no
-        // transmission load is waited for in the 100-step loop
-        g_t3z = true;
-        b2 += "    const int nz_ = t3n[k];\n    for (int q_ = 0; q_ < nz_; q_++) {\n      const int pk_ = t3z[k * 32 + q_], e = pk_ >> 2;\n"
-              "      const double t = (pk_ & 3) == 0 ? 1.0 : (pk_ & 3) == 1 ? 0.5 : 0.25;\n";
-      } else b2 += "    for (int e = 0; e < " + nsq + "; e++) {\n      const double t = " + tt(csex, "e", "k", slot != 255) + ";\n";
-      for (int a = 0; a <= dw; a++) b2 += "      s[" + S(a) + "] = fma(t, W[" + TBs + " + e * " + S(ww) + " + " + S(a) + "], s[" + S(a) + "]);\n";
-      b2 += "    }\n    double t[" + S(g.e + 1) + "];\n";
-      for (int c = 0; c <= g.e; c++) b2 += "    t[" + S(c) + "] = W[" + PO(off_) + " + k * " + S(capP[off_]) + " + " + S(c) + "];\n";
-      for (int a = 0; a <= g.e + dw; a++) {
-        std::string acc;
-        for (int c = std::max(0, a - dw); c <= std::min(a, g.e); c++)
-          acc = acc.empty() ? "t[" + S(c) + "] * s[" + S(a - c) + "]" : "fma(t[" + S(c) + "], s[" + S(a - c) + "], " + acc + ")";
-        b2 += "    W[" + PO(off_) + " + k * " + S(capP[off_]) + " + " + S(a) + "] = " + acc + ";\n";
-      }
-      code += lanes(NS, "k", b2) + "  wave_sync();\n";
+// A bi-allelic type-1 step k (peelOffspring2Parents_BA): lanes over the pairs e, S(e) = sum_k T(e, k) P_off[k] in
+// registers, then M(e) *= S(e) in place
+void emit_type1_step(const WaveFamily& A, int k, std::string& code) {
+  const StepDeg g = A.sd[k];
+  const int off_ = A.from0(k), csex = A.F.sex[off_], pcap = A.capP[off_], slot = A.slot(k);
+  std::string b = "      double s[" + S(g.a + 1) + "];\n";
+  for (int a = 0; a <= g.a; a++) {
+    b += "      s[" + S(a) + "] = 0.0;\n";
+    b += "#pragma unroll\n      for (int k = 0; k < " + S(A.NS) + "; k++) s[" + S(a) + "] = fma(" + tt(A, csex, "e", "k", false) + ", W[" +
+         A.PO(off_) + " + k * " + S(pcap) + " + " + S(a) + "], s[" + S(a) + "]);\n";
+  }
+  const std::string me = A.MO(slot) + " + e * " + S(A.mcap(slot));
+  if (A.create(k)) {
+    for (int a = 0; a <= g.a; a++) b += "      W[" + me + " + " + S(a) + "] = s[" + S(a) + "];\n";
+  } else {
+    b += "      double m[" + S(g.b + 1) + "];\n";
+    for (int c = 0; c <= g.b; c++) b += "      m[" + S(c) + "] = W[" + me + " + " + S(c) + "];\n";
+    for (int a = 0; a <= g.a + g.b; a++) b += "      W[" + me + " + " + S(a) + "] = " + conv("m", g.b, "s", g.a, a) + ";\n";
+  }
+  code += pair_lanes(A, b);
+}
+
+// A run of consecutive 10-state type-1 steps (this part's; they only read offspring partials and their own marriage
+// partial) is one phase: lanes over the pairs (lane, lane + 32, ... < 100), one pass over k for every step of the run
+// (each offspring coefficient read from LDS once for the lane's pairs: wave-uniform broadcasts), then per marriage
+// partial the steps' products chained in registers and one write -- the same operations in the same order as step by
+// step.  sp: the run's founder-sparse rows (only the pairs of the founder's non-zero states are computed).
+void emit_type1_run(const WaveFamily& A, const std::vector<int>& run, const Sparse& sp, std::string& code) {
+  const int n = A.n;
+  std::vector<int> slots;   // the marriage partials the run writes, in order of first use
+  for (int k2 : run)
+    if (std::find(slots.begin(), slots.end(), A.slot(k2)) == slots.end()) slots.push_back(A.slot(k2));
+  const bool sparse = !sp.terms.empty();
+  const int nsp = 10 * (int)sp.terms.size();   // (sparse: the rows, passes of kWl lanes over them)
+  const int npair = sparse ? (nsp + kWl - 1) / kWl : (100 + kWl - 1) / kWl;
+  std::string c1 = "  {\n";
+  if (sparse) {   // pass pr: row p = lane + pr kWl (state o of the spouse, term qi of the founder's support); rows past
+                  // the support compute an in-range pair and store nothing
+    const std::string gq[3] = {"g11", "g12", "g22"};
+    for (int pr = 0; pr < npair; pr++) {
+      const std::string P = S(pr), qi = "qi" + P;
+      std::string sF = gq[sp.terms.back().first];
+      for (int q = (int)sp.terms.size() - 2; q >= 0; q--) sF = qi + " == " + S(q) + " ? " + gq[sp.terms[q].first] + " : " + sF;
+      c1 += "    const int p" + P + " = lane + " + S(pr * kWl) + ", " + qi + " = p" + P + " / 10, o" + P + " = p" + P + " - " + qi +
+            " * 10, sF" + P + " = " + sF + ";\n    const int e" + P + " = " +
+            (sp.father ? "sF" + P + " * 10 + o" + P : "o" + P + " * 10 + sF" + P) + ";\n";
+    }
+  } else
+    for (int pr = 1; pr < npair; pr++)
+      c1 += "    const int e" + S(pr) + " = lane + " + S(pr * kWl) + ", e" + S(pr) + "c = e" + S(pr) + " < 100 ? e" + S(pr) + " : lane;\n";
+  for (size_t q = 0; q < run.size(); q++) {
+    const int ga = A.sd[run[q]].a;
+    for (int pr = 0; pr < npair; pr++) {
+      c1 += "    double s" + S(pr) + "_" + S(q) + "[" + S(ga + 1) + "];\n";
+      for (int a = 0; a <= ga; a++) c1 += "    s" + S(pr) + "_" + S(q) + "[" + S(a) + "] = 0.0;\n";
     }
   }
-  const int D = dP[fin];
-  *ops = M * (nops + (part == 1 ? 0.0 : (double)(D + 1) * NS));
-  if (getenv("PM_JIT_LAYOUT"))
-    fprintf(stderr, "occupancy %s part %d WL %d: %.0f FP64 ops / %.0f lane slots = %.3f\n", name.c_str(), part, g_wl, nops, lane_slots,
-            lane_slots > 0 ? nops / lane_slots : 0.0);
-  if (part != 1) {
-    code += lanes(D + 1, "a", "    double s = 0.0;\n#pragma unroll\n    for (int i = 0; i < " + nsS + "; i++) s += W[" + PO(fin) + " + i * " +
-                                  S(capP[fin]) + " + a];\n    out[" + std::string(mc ? "c * ostr + " : "") + "(size_t)a * os] = s;\n");
-    code += "  if (lane < " + S(M) + ") out[" + std::string(mc ? "lane * ostr + " : "") + "(size_t)(dcap - 1) * os] = " + S(D) + ".0;\n  wave_sync();\n";
+  // (k unrolled by 2 only: fully unrolled, the scheduler hoists every offspring coefficient's LDS read and spills)
+  c1 += "#pragma unroll 2\n    for (int k = 0; k < 10; k++) {\n";
+  c1 += sparse ? "      const double t0 = t10dn[e0 * 10 + k]" : "      const double t0 = t10dn[lane * 10 + k]";   // the rows of this lane's pairs
+  for (int pr = 1; pr < npair; pr++) c1 += ", t" + S(pr) + " = t10dn[e" + S(pr) + (sparse ? "" : "c") + " * 10 + k]";
+  c1 += ";\n";
+  for (size_t q = 0; q < run.size(); q++) {
+    const int offq = A.from0(run[q]), ga = A.sd[run[q]].a;
+    for (int a = 0; a <= ga; a++) {
+      c1 += A.penp[offq] ? "      {\n        const double p = PEN[k * " + S(n) + " + " + S(offq) + "];\n"
+                         : "      {\n        const double p = W[" + A.PO(offq) + " + k * " + S(A.capP[offq]) + " + " + S(a) + "];\n";
+      for (int pr = 0; pr < npair; pr++)
+        c1 += "        s" + S(pr) + "_" + S(q) + "[" + S(a) + "] = fma(t" + S(pr) + ", p, s" + S(pr) + "_" + S(q) + "[" + S(a) + "]);\n";
+      c1 += "      }\n";
+    }
   }
-  return "__device__ __forceinline__ void " + name +
+  c1 += "    }\n";
+  // per pair: each marriage partial chained through its steps in registers, one write
+  for (int pr = 0; pr < npair; pr++) {
+    const std::string sq_ = "s" + S(pr) + "_", e = sp.compact ? "p" + S(pr) : sparse ? "e" + S(pr) : pr ? "e" + S(pr) : "lane";
+    c1 += sparse ? "    if (p" + S(pr) + " < " + S(nsp) + ") {\n" : pr ? "    if (e" + S(pr) + " < 100) {\n" : "    {\n";
+    int cid = 0;
+    for (int sl2 : slots) {
+      const std::string mev = A.MO(sl2) + " + " + e + " * " + S(A.mcap(sl2));
+      std::string cur;   // the register array holding the slot's current coefficients
+      int dcur = -1;
+      for (size_t q = 0; q < run.size(); q++) {
+        if (A.slot(run[q]) != sl2) continue;
+        const int ga = A.sd[run[q]].a, gb = A.sd[run[q]].b;
+        const std::string sq = sq_ + S(q);
+        if (A.create(run[q])) { cur = sq; dcur = ga; continue; }
+        if (dcur < 0) {   // the slot's coefficients so far, from LDS
+          cur = "m" + S(pr) + "_" + S(cid++);
+          c1 += "      double " + cur + "[" + S(gb + 1) + "];\n";
+          for (int c = 0; c <= gb; c++) c1 += "      " + cur + "[" + S(c) + "] = W[" + mev + " + " + S(c) + "];\n";
+          dcur = gb;
+        }
+        const std::string nx = "m" + S(pr) + "_" + S(cid++);
+        c1 += "      double " + nx + "[" + S(ga + gb + 1) + "];\n";
+        for (int a = 0; a <= ga + gb; a++) c1 += "      " + nx + "[" + S(a) + "] = " + conv(cur, gb, sq, ga, a) + ";\n";
+        cur = nx;
+        dcur = ga + gb;
+      }
+      for (int a = 0; a <= dcur; a++) c1 += "      W[" + mev + " + " + S(a) + "] = " + cur + "[" + S(a) + "];\n";
+    }
+    c1 += "    }\n";
+  }
+  code += c1 + "  }\n  wave_sync();\n";
+}
+
+// The independent type-2 steps of one shape that follow step k (this part's, 10 states): they share one phase, 16 lanes
+// per step, the lane's step selecting its partials' offsets
+std::vector<int> type2_run(const WaveFamily& A, int k) {
+  std::vector<int> run{k};
+  if (A.NS != 10) return run;
+  auto sig2 = [&](int k2) {
+    const int f2 = A.from0(k2), t2 = A.to0(k2), s2 = A.slot(k2);
+    return std::vector<int>{A.pristine[k2], A.sd[k2].a, A.sd[k2].b, A.sd[k2].c, s2 == 255, A.capP[f2], A.capP[t2], s2 == 255 ? 0 : A.mcap(s2),
+                            A.d0[f2], (int)A.crows.count(s2), (int)A.penf[f2], (int)A.iinit[t2], A.founder(t2),
+                            A.founder(t2) ? A.fdeg(t2) : -1};
+  };
+  const std::vector<int> sg0 = sig2(k);
+  for (int k2 = k + 1; k2 < A.nst && (int)run.size() < kWl / 16; k2++) {
+    if (!A.inpart(k2)) continue;
+    if (A.type(k2) != 2 || sig2(k2) != sg0) break;
+    const int f2 = A.from0(k2), t2 = A.to0(k2);
+    bool indep = true;
+    for (int k3 : run)
+      if (t2 == A.to0(k3) || f2 == A.to0(k3) || A.from0(k3) == t2) indep = false;
+    if (!indep) break;
+    run.push_back(k2);
+  }
+  return run;
+}
+
+// Type-2 step run[0], or the packed run of type2_run (peelSpouse2Spouse_BA): lanes over i, S(i) = sum_j P_from[j]
+// M(j, i) in registers, then P_to[i] *= S(i) in place
+void emit_type2(const WaveFamily& A, const std::vector<int>& run, std::string& code) {
+  const int kstep = run[0], n = A.n, NS = A.NS;
+  const StepDeg g = A.sd[kstep];
+  const int sf = A.from0(kstep), stt = A.to0(kstep), slot = A.slot(kstep), fcap = A.capP[sf], tcap = A.capP[stt];
+  const int ds = g.a + g.b;
+  const bool packed = run.size() > 1;
+  const std::string nsS = S(NS);
+  // q_ == 0 ? f(run[0]) : ... : f(run.back()): the value of the lane group's step
+  auto sel = [&](const std::function<std::string(int)>& f) {
+    std::string e = f(run.back());
+    for (int q = (int)run.size() - 2; q >= 0; q--) e = "q_ == " + S(q) + " ? " + f(run[q]) + " : " + e;
+    return e;
+  };
+  std::string OF = A.PO(sf), OT = A.PO(stt), OM = slot == 255 ? "" : A.MO(slot), pre;
+  if (packed) {
+    pre = "      const int of_ = " + sel([&](int k2) { return A.PO(A.from0(k2)); }) +
+          ";\n      const int ot_ = " + sel([&](int k2) { return A.PO(A.to0(k2)); }) + ";\n";
+    if (slot != 255) {   // (and the marriage partial's orientation: M(i, j) or M(j, i))
+      pre += "      const int om_ = " + sel([&](int k2) { return A.MO(A.slot(k2)); }) + ";\n";
+      pre += "      const int si_ = " + sel([&](int k2) { return std::string(A.fa2mo(k2) ? "1" : nsS); }) + ", sj_ = " +
+             sel([&](int k2) { return std::string(A.fa2mo(k2) ? nsS : "1"); }) + ";\n";
+    }
+    OF = "of_"; OT = "ot_"; OM = "om_";
+  }
+  const std::string me = packed ? "(i * si_ + j * sj_)" : A.fa2mo(kstep) ? "(j * " + nsS + " + i)" : "(i * " + nsS + " + j)";
+
+  std::string b = "    double s[" + S(ds + 1) + "];\n";
+  for (int a = 0; a <= ds; a++) b += "    s[" + S(a) + "] = 0.0;\n";
+  if (A.pristine[kstep]) {
+    // the founder's partial is prior x penetrance: state g11 / g12 / g22 holds one monomial, at coefficient
+    // 2 - q (degree 2: q = 0, 1, 2), 1 / - / 0 (degree 1: no geno12) or 0 (degree 0); the other states are zero.
+    // The sum visits j in the dense loop's order and skips the zero terms (fma(0, g, s) == s), so it is
+    // bit-identical to the dense sum (q in the dense loop's coefficient order u = 0, 1, 2 at one j, should two of
+    // the genotypes coincide)
+    // No loop over j: the terms' states are wave-uniform, so their order by j (stable: ties keep the coefficient
+    // order) is one of at most 6, chosen once by a uniform switch; each case adds the terms in that order
+    const std::string gq[3] = {"g11", "g12", "g22"};
+    const std::vector<std::pair<int, int>> tm = A.pterms(sf);
+    auto term = [&](int q, int u, int qpos) {
+      std::string t = "      {\n        const int j = " + gq[q] + ";\n";
+      if (A.penf[sf]) {   // the penetrance the init phase would have stored, from PEN (one read: the person index selected;
+                          // x 2 for the heterozygote's coefficient)
+        t += "        const double pj_ = PEN[j * " + S(n) + " + (" + sel([&](int k2) { return S(A.from0(k2)); }) + ")];\n";
+        t += (!A.top && A.d0[sf] == 2 && q == 1) ? "        const double f = 2 * pj_;\n" : "        const double f = pj_;\n";
+      } else t += "        const double f = W[" + OF + " + j * " + S(fcap) + " + " + S(u) + "];\n";
+      if (slot == 255) t += "        s[" + S(u) + "] += f;\n";
+      else {
+        const std::string mr = A.crows.count(slot) ? "(" + S(qpos * 10) + " + i)" : me;   // (compact rows)
+        for (int v = 0; v <= g.b; v++)
+          t += "        s[" + S(u + v) + "] = fma(f, W[" + OM + " + " + mr + " * " + S(A.mcap(slot)) + " + " + S(v) + "], s[" + S(u + v) + "]);\n";
+      }
+      return t + "      }\n";
+    };
+    const int nt = (int)tm.size();
+    if (nt == 1) b += term(tm[0].first, tm[0].second, 0);
+    else {
+      // bit c of the case: term a (of pair c) is not after term b, in the terms' order a < b
+      std::vector<std::pair<int, int>> prs;
+      for (int a = 0; a < nt; a++)
+        for (int c = a + 1; c < nt; c++) prs.push_back({a, c});
+      std::string key;
+      for (size_t c = 0; c < prs.size(); c++)
+        key += std::string(c ? " | " : "") + "((" + gq[tm[prs[c].first].first] + " <= " + gq[tm[prs[c].second].first] + ") << " + S(c) + ")";
+      b += "    switch (" + key + ") {\n";
+      for (int cs = 0; cs < (1 << prs.size()); cs++) {
+        std::vector<int> ord(nt);
+        for (int a = 0; a < nt; a++) ord[a] = a;
+        auto before = [&](int x, int y) {   // x before y in this case
+          for (size_t c = 0; c < prs.size(); c++) {
+            if (prs[c].first == x && prs[c].second == y) return ((cs >> c) & 1) != 0;
+            if (prs[c].first == y && prs[c].second == x) return ((cs >> c) & 1) == 0;
+          }
+          return x < y;
+        };
+        std::stable_sort(ord.begin(), ord.end(), before);
+        b += "      case " + S(cs) + ":\n";
+        for (int a : ord) b += term(tm[a].first, tm[a].second, a);
+        b += "      break;\n";
+      }
+      b += "    }\n";
+    }
+  } else if (slot == 255) {
+    for (int a = 0; a <= ds; a++)
+      b += "#pragma unroll\n    for (int j = 0; j < " + nsS + "; j++) s[" + S(a) + "] += W[" + OF + " + j * " + S(fcap) + " + " +
+           S(a) + "];\n";
+  } else {
+    b += std::string(packed ? "#pragma unroll 2" : "#pragma unroll") + "\n    for (int j = 0; j < " + nsS + "; j++) {\n";
+    for (int u = 0; u <= g.a; u++) b += "      const double f" + S(u) + " = W[" + OF + " + j * " + S(fcap) + " + " + S(u) + "];\n";
+    for (int v = 0; v <= g.b; v++) b += "      const double g" + S(v) + " = W[" + OM + " + " + me + " * " + S(A.mcap(slot)) + " + " + S(v) + "];\n";
+    for (int u = 0; u <= g.a; u++)
+      for (int v = 0; v <= g.b; v++) b += "      s[" + S(u + v) + "] = fma(f" + S(u) + ", g" + S(v) + ", s[" + S(u + v) + "]);\n";
+    b += "    }\n";
+  }
+  b += "    double t[" + S(g.c + 1) + "];\n";
+  if (A.iinit[stt]) {   // the initial partial at state i (InitializePartials x SetFounderPriors), of the lane group's to-person
+    const bool fo2 = A.founder(stt);
+    const int dfull2 = !fo2 ? 0 : A.fdeg(stt);
+    const int d2 = A.d0[stt];
+    b += "    const double pen_ = PEN[i * " + S(n) + " + (" + sel([&](int k2) { return S(A.to0(k2)); }) + ")];\n";
+    b += "    const int qi_ = i == g11 ? 0 : i == g12 ? 1 : i == g22 ? 2 : 3;\n    (void)qi_;\n";
+    for (int c = 0; c <= g.c; c++) {
+      std::string v = "0.0";
+      if (!fo2) v = c == 0 ? "pen_" : "0.0";
+      else if (A.top && dfull2 > 0) v = c == 0 ? "(qi_ == 0 ? pen_ : 0.0)" : "0.0";
+      else if (d2 == 2) v = c == 0 ? "(qi_ == 2 ? pen_ : 0.0)" : c == 1 ? "(qi_ == 1 ? 2 * pen_ : 0.0)" : c == 2 ? "(qi_ == 0 ? pen_ : 0.0)" : "0.0";
+      else if (d2 == 1) v = c == 0 ? "(qi_ == 2 ? pen_ : 0.0)" : c == 1 ? "(qi_ == 0 ? pen_ : 0.0)" : "0.0";
+      else v = c == 0 ? "(qi_ != 3 ? pen_ : 0.0)" : "0.0";
+      b += "    t[" + S(c) + "] = " + v + ";\n";
+    }
+  } else
+    for (int c = 0; c <= g.c; c++) b += "    t[" + S(c) + "] = W[" + OT + " + i * " + S(tcap) + " + " + S(c) + "];\n";
+  for (int a = 0; a <= g.c + ds; a++) b += "    W[" + OT + " + i * " + S(tcap) + " + " + S(a) + "] = " + conv("t", g.c, "s", ds, a) + ";\n";
+  if (packed)
+    code += "  {\n    const int q_ = lane >> 4, i = lane & 15;\n    if (q_ < " + S(run.size()) + " && i < " + nsS + ") {\n" + pre + b +
+            "    }\n  }\n  wave_sync();\n";
+  else code += lanes(NS, "i", b) + "  wave_sync();\n";
+}
+
+// the second half of a type-3 step: lanes over the child states k, P_off[k] *= S(k), S(k) = the sum `loop` accumulates
+// into s[] over the products at W[TB + ...]
+void emit_type3_child(const WaveFamily& A, int k, const std::string& loop, std::string& code) {
+  const StepDeg g = A.sd[k];
+  const int off_ = A.to0(k), dw = g.a + g.b + g.c;
+  std::string b2 = "    double s[" + S(dw + 1) + "];\n";
+  for (int a = 0; a <= dw; a++) b2 += "    s[" + S(a) + "] = 0.0;\n";
+  b2 += loop + "    }\n    double t[" + S(g.e + 1) + "];\n";
+  for (int c = 0; c <= g.e; c++) b2 += "    t[" + S(c) + "] = W[" + A.PO(off_) + " + k * " + S(A.capP[off_]) + " + " + S(c) + "];\n";
+  for (int a = 0; a <= g.e + dw; a++)
+    b2 += "    W[" + A.PO(off_) + " + k * " + S(A.capP[off_]) + " + " + S(a) + "] = " + conv("t", g.e, "s", dw, a) + ";\n";
+  code += lanes(A.NS, "k", b2) + "  wave_sync();\n";
+}
+// the first half: w = P_fa[i] M(e) P_mo[j] of the lane's pair (i, j, e) into W[TB + at * (dw + 1) ...]
+std::string type3_products(const WaveFamily& A, int k, const std::string& at) {
+  const StepDeg g = A.sd[k];
+  const int fa = A.from0(k), mo_ = A.from1(k), slot = A.slot(k), dw = g.a + g.b + g.c, ww = dw + 1;
+  std::string b = "      double w[" + S(ww) + "];\n";
+  for (int a = 0; a <= dw; a++) b += "      w[" + S(a) + "] = 0.0;\n";
+  for (int u = 0; u <= g.a; u++)
+    for (int v = 0; v <= g.b; v++)
+      for (int c = 0; c <= g.c; c++) {
+        const std::string m = slot == 255 ? "" : " * W[" + A.MO(slot) + " + e * " + S(A.mcap(slot)) + " + " + S(v) + "]";
+        b += "      w[" + S(u + v + c) + "] = fma(W[" + A.PO(fa) + " + i * " + S(A.capP[fa]) + " + " + S(u) + "]" + m + ", W[" +
+             A.PO(mo_) + " + j * " + S(A.capP[mo_]) + " + " + S(c) + "], w[" + S(u + v + c) + "]);\n";
+      }
+  for (int a = 0; a <= dw; a++) b += "      W[" + S(A.TB) + " + " + at + " * " + S(ww) + " + " + S(a) + "] = w[" + S(a) + "];\n";
+  return b;
+}
+
+// Dense type-3 step k (peelParents2Offspring_BA): W(e) = P_fa[i] M(e) P_mo[j] -> LDS; lanes over k: S(k) = sum_e T(e, k)
+// W(e), P_off[k] *= S(k) in place.  Returns whether the step reads the LDS list t3z / t3n.
+bool emit_type3_dense(const WaveFamily& A, int k, const Opts& opt, std::string& code) {
+  const StepDeg g = A.sd[k];
+  const int csex = A.F.sex[A.to0(k)], slot = A.slot(k), ww = g.a + g.b + g.c + 1;
+  const std::string nsS = S(A.NS);
+  code += pair_lanes(A, "      const int i = e / " + nsS + ", j = e - i * " + nsS + ";\n" + type3_products(A, k, "e"));
+  // 10 states, with a marriage partial: the plain transmission (:1391) is the Mendelian table, 16-31 of a child state's
+  // 100 parent pairs are non-zero (1, 1/2 or 1/4).  Each lane k runs over its non-zero pairs only, in ascending e (the
+  // LDS list t3z, e << 2 | value code, filled from kT3z / kT3n at kernel start): the pairs skipped would add +0 (T = 0, W
+  // finite and >= 0), so every sum keeps its bits -- and no transmission load is waited for in the 100-step loop
+  const bool t3z = A.NS == 10 && slot != 255 && opt.t3z;
+  std::string loop = t3z ? "    const int nz_ = t3n[k];\n    for (int q_ = 0; q_ < nz_; q_++) {\n      const int pk_ = t3z[k * 32 + q_], e = pk_ >> 2;\n"
+                           "      const double t = (pk_ & 3) == 0 ? 1.0 : (pk_ & 3) == 1 ? 0.5 : 0.25;\n"
+                         : "    for (int e = 0; e < " + S(A.NS * A.NS) + "; e++) {\n      const double t = " + tt(A, csex, "e", "k", slot != 255) + ";\n";
+  for (int a = 0; a < ww; a++) loop += "      s[" + S(a) + "] = fma(t, W[" + S(A.TB) + " + e * " + S(ww) + " + " + S(a) + "], s[" + S(a) + "]);\n";
+  emit_type3_child(A, k, loop, code);
+  return t3z;
+}
+
+// Founder-sparse type-3 step k (10 states): a founder's partial is prior x penetrance times whatever multiplied into
+// it -- zero outside the 1-3 states of its prior (the site's g11, g12, g22; pterms) -- so W(e) = P_fa[i] M(e) P_mo[j]
+// is zero off those pairs, and so is every term T(e, k) W(e) they would add (+0: the sums keep their bits).  Only
+// the nI x nJ pairs (i, j) in ascending e are formed (lanes over them) and summed (in the same ascending e order),
+// instead of all 100.  The states of a founder's support are sorted at run time (wave-uniform).
+void emit_type3_sparse(const WaveFamily& A, int k, std::string& code) {
+  const StepDeg g = A.sd[k];
+  const int csex = A.F.sex[A.to0(k)], slot = A.slot(k), ww = g.a + g.b + g.c + 1;
+  const std::string nsS = S(A.NS);
+  auto support = [&](int f, const std::string& pre) -> std::pair<int, std::string> {
+    if (!A.founder(f)) return {10, ""};
+    const auto t = A.pterms(f);
+    std::string c;
+    for (size_t q = 0; q < t.size(); q++)
+      c += "  int " + pre + S(q) + " = " + (t[q].first == 0 ? "g11" : t[q].first == 1 ? "g12" : "g22") + ";\n";
+    auto sw = [&](int a, int b2) {
+      return "  if (" + pre + S(a) + " > " + pre + S(b2) + ") { const int x_ = " + pre + S(a) + "; " + pre + S(a) + " = " + pre + S(b2) +
+             "; " + pre + S(b2) + " = x_; }\n";
+    };
+    if (t.size() >= 2) c += sw(0, 1);
+    if (t.size() == 3) c += sw(1, 2) + sw(0, 1);
+    return {(int)t.size(), c};
+  };
+  const std::string pI = "sI" + S(k) + "_", pJ = "sJ" + S(k) + "_";
+  const auto sI = support(A.from0(k), pI), sJ = support(A.from1(k), pJ);
+  const int nI = sI.first, nJ = sJ.first, NP = nI * nJ;
+  auto pick = [&](const std::string& pre, int nn, const std::string& idx) {   // the idx-th state of a support
+    if (nn == 10) return idx;
+    std::string r = pre + S(nn - 1);
+    for (int q = nn - 2; q >= 0; q--) r = "(" + idx + " == " + S(q) + " ? " + pre + S(q) + " : " + r + ")";
+    return r;
+  };
+  code += sI.second + sJ.second;
+  const std::string b = "      const int ia = p / " + S(nJ) + ", jb = p - ia * " + S(nJ) + ";\n      const int i = " + pick(pI, nI, "ia") +
+                        ", j = " + pick(pJ, nJ, "jb") + ", e = i * " + nsS + " + j;\n" + type3_products(A, k, "p");
+  code += "#pragma unroll\n  for (int r = 0; r < " + S((NP + kWl - 1) / kWl) + "; r++) {\n    const int p = lane + " + S(kWl) + " * r;\n    if (p < " +
+          S(NP) + ") {\n" + b + "    }\n  }\n  wave_sync();\n";
+  std::string loop = "    for (int p = 0; p < " + S(NP) + "; p++) {\n      const int ia = p / " + S(nJ) + ", jb = p - ia * " + S(nJ) + ";\n      const int e = " +
+                     pick(pI, nI, "ia") + " * " + nsS + " + " + pick(pJ, nJ, "jb") + ";\n      const double t = " + tt(A, csex, "e", "k", slot != 255) + ";\n";
+  for (int a = 0; a < ww; a++) loop += "      s[" + S(a) + "] = fma(t, W[" + S(A.TB) + " + p * " + S(ww) + " + " + S(a) + "], s[" + S(a) + "]);\n";
+  emit_type3_child(A, k, loop, code);
+}
+
+// CalculateLikelihood_BA: the final person's partials summed over the states, one lane per coefficient, and the degree word
+void emit_final_sum(const WaveFamily& A, int fin, std::string& code) {
+  const int D = A.dP[fin];
+  code += lanes(D + 1, "a", "    double s = 0.0;\n#pragma unroll\n    for (int i = 0; i < " + S(A.NS) + "; i++) s += W[" + A.PO(fin) + " + i * " +
+                                S(A.capP[fin]) + " + a];\n    out[(size_t)a * os] = s;\n");
+  code += "  if (lane < 1) out[(size_t)(dcap - 1) * os] = " + S(D) + ".0;\n  wave_sync();\n";
+}
+
+// The device function of an analysed family: the phases in schedule order.  ops: the FP64 operations the generated
+// phases perform (summed over their work elements: the useful lane-operations, whatever the lanes' occupancy);
+// *uses_t3z is set when a phase reads the Mendelian LDS list.
+std::string emit_wave_family(const WaveFamily& A, const Opts& opt, double* ops, bool* uses_t3z) {
+  const int nst = A.nst, NS = A.NS;
+  std::string code;
+  emit_initial_partials(A, code);
+  double nops = 0, lane_slots = 0;
+  std::vector<char> done(nst, 0);         // steps emitted with the first step of their run
+  std::vector<double> eff2(nst, 0.0);     // packed type-2 runs: the run's lane occupancy (10 r of kWl lanes)
+  std::vector<double> frac1(nst, 1.0);    // type-1 steps: the fraction of the 100 pairs computed (founder-sparse rows)
+  for (int k = 0; k < nst; k++) {
+    if (!A.inpart(k)) continue;
+    const StepDeg g = A.sd[k];
+    const int type = A.type(k), slot = A.slot(k);
+    // this step's FP64 operations (per item), and the lane slots they occupy (PM_JIT_LAYOUT: the static lane
+    // occupancy -- a phase over E elements on a family's kWl lanes runs ceil(E / kWl) passes of kWl lanes; a packed
+    // run of r type-2 steps fills 10 r of the kWl lanes; PM_JIT_STEPS: per step)
+    const double ns = NS, before = nops;
+    auto occ = [&](double E, double lanes) { return E / (std::ceil(E / lanes) * lanes); };
+    auto ops1 = [&](double pairs) { return pairs * ((g.a + 1) * ns + (A.create(k) ? 0 : (g.a + 1) * (g.b + 1))); };
+    double eff = 1.0;
+    if (type == 1) {
+      nops += ops1(frac1[k] * ns * ns);
+      eff = occ(frac1[k] * ns * ns, kWl);
+    } else if (type == 2) {
+      const int ds = g.a + g.b;
+      if (A.pristine[k]) nops += ns * ((double)A.pterms(A.from0(k)).size() * (slot == 255 ? 1 : (g.b + 1)) + (g.c + 1) * (ds + 1));
+      else nops += ns * ((slot == 255 ? (ds + 1) * ns : ns * (g.a + 1) * (g.b + 1)) + (g.c + 1) * (ds + 1));
+      eff = eff2[k] > 0 ? eff2[k] : occ(ns, kWl);   // (a packed run's first step: corrected below)
+    } else {
+      const int dw = g.a + g.b + g.c;
+      double np_ = ns * ns;   // (founder-sparse: the pairs of the founders' supports only)
+      if (A.sp3[k]) {
+        const int f0 = A.from0(k), f1 = A.from1(k);
+        np_ = (double)(A.founder(f0) ? (int)A.pterms(f0).size() : 10) * (A.founder(f1) ? (int)A.pterms(f1).size() : 10);
+      }
+      const double o1 = np_ * (g.a + 1) * (g.b + 1) * (g.c + 1) * (slot == 255 ? 1 : 2), o2 = ns * (np_ * (dw + 1) + (g.e + 1) * (dw + 1));
+      nops += o1 + o2;
+      eff = (o1 + o2) / (o1 / occ(np_, kWl) + o2 / occ(ns, kWl));
+    }
+    lane_slots += (nops - before) / eff;
+    const double step_ops = nops - before;
+    if (opt.steps)
+      fprintf(stderr, "  step %s part %d M 1 k %d type %d ops %.0f eff %.3f\n", A.name.c_str(), A.part, k, type, step_ops, eff);
+    if (done[k]) continue;
+    if (type == 1 && NS == 10) {
+      const std::vector<int> run = A.run_of(k);
+      const Sparse sp = A.sparse_of(run);
+      for (int k2 : run) done[k2] = 1;
+      if (!sp.terms.empty()) {   // (this step, the run's first, was counted at 100 pairs above)
+        const double fr = 10.0 * sp.terms.size() / 100.0;
+        nops -= ops1((1.0 - fr) * 100.0);
+        for (int k2 : run) frac1[k2] = fr;
+      }
+      emit_type1_run(A, run, sp, code);
+    } else if (type == 1) emit_type1_step(A, k, code);
+    else if (type == 2) {
+      const std::vector<int> run = type2_run(A, k);
+      if (run.size() > 1) {
+        for (int k2 : run) { eff2[k2] = (double)NS * run.size() / kWl; done[k2] = 1; }
+        lane_slots += step_ops / eff2[k] - step_ops / eff;
+      }
+      emit_type2(A, run, code);
+    } else if (A.sp3[k]) emit_type3_sparse(A, k, code);
+    else if (emit_type3_dense(A, k, opt, code)) *uses_t3z = true;
+  }
+  const int fin = A.to0(nst - 1);
+  *ops = nops + (A.part == 1 ? 0.0 : (double)(A.dP[fin] + 1) * NS);
+  if (opt.layout)
+    fprintf(stderr, "occupancy %s part %d WL %d: %.0f FP64 ops / %.0f lane slots = %.3f\n", A.name.c_str(), A.part, kWl, nops, lane_slots,
+            lane_slots > 0 ? nops / lane_slots : 0.0);
+  if (A.part != 1) emit_final_sum(A, fin, code);
+  // (tr0 / tr1: arguments the functions no longer read; the kernel text is pinned, see tests/test_cpu_jit_source.py)
+  return "__device__ __forceinline__ void " + A.name +
          "(const uint8_t* __restrict__ pl, size_t np, const uint8_t* __restrict__ P11, const uint8_t* __restrict__ P12, "
          "const uint8_t* __restrict__ P22, int p0, int gg11, int gg12, int gg22, const double* lk, const double* __restrict__ t10, "
          "const double* __restrict__ t10dn, const double* tb, const double* tr0, const double* tr1, double* W, int lane, "
          "double* __restrict__ out, int os, int dcap, size_t ostr, const double* PEN) {\n" + code + "}\n";
 }
 
-// The site's penetrances of a family, lk[pl[g][p0 + i]] for the 10 genotypes g, into the wave's LDS table PEN[g * n + i]
+// The site's penetrances of a family, lk[pl[g][p0 + i]] for the 10 genotypes g, into the family's LDS table PEN[g * n + i]
 // (one coalesced pass per (site, family) instead of a dependent global load per person and variant)
 std::string gen_pen_fill(int n, const std::string& name) {
   const std::string N = std::to_string(n);
   return "__device__ __forceinline__ void " + name + "(const uint8_t* __restrict__ pl, size_t np, int p0, const double* lk, double* PEN, "
-         "int lane) {\n  for (int e = lane; e < " + std::to_string(10 * n) + "; e += " + std::to_string(g_wl) + ") {\n    const int g = e / " + N + ", i = e - g * " + N +
+         "int lane) {\n  for (int e = lane; e < " + std::to_string(10 * n) + "; e += " + std::to_string(kWl) + ") {\n    const int g = e / " + N + ", i = e - g * " + N +
          ";\n    PEN[e] = lk[pl[(size_t)g * np + p0 + i]];\n  }\n  wave_sync();\n}\n";
 }
 
-// fns: 3 variants per shape (bi-allelic, 10-state, top); parts: per shape the 10-state leaf prefix, the 10-state rest,
-// the top variant's rest and (pps == 4) the 10-state rest of three items at once
+// fns: 3 variants per shape (bi-allelic, 10-state, top); parts: 3 per shape, the 10-state leaf prefix, the 10-state rest
+// and the top variant's rest.
+// The kernel's text is pinned byte for byte (tests/test_cpu_jit_source.py): a few of its lines still show what earlier
+// switches substituted (`true &&`, `(true:`, `if (false && ...)`, the unused tr0 / tr1 rows) -- dead text the compiler
+// drops, to go with the next change that is meant to alter the kernels.
 std::string gen_wave_kernel(const std::vector<std::string>& fns, const std::vector<std::string>& parts, const std::vector<std::string>& pens,
-                            const std::vector<int>& shape_ns, int pps, int ws, int pensz, int wpb, bool parts_only) {
-  // prefetch registers per lane (0: families too large; up to 4, 8 at 16 lanes per family)
-  const int npf = pensz <= (g_wl >= 32 ? 4 : 8) * g_wl ? (pensz + g_wl - 1) / g_wl : 0;
+                            const std::vector<int>& shape_ns, int ws, int pensz, int wpb, bool parts_only, bool uses_t3z, const Opts& opt) {
+  // prefetch registers per lane (0: families too large; up to 4)
+  const int npf = pensz <= 4 * kWl ? (pensz + kWl - 1) / kWl : 0;
   // wave_sync: the phases' LDS hand-over inside one wave.  A wave's LDS instructions execute in issue order, so a
-  // read after a write sees it without waiting for the write; only the compiler must not move accesses across
-  // (g_fence, the default: wavefront-scope release / acquire fences, which wait for the outstanding LDS accesses --
-  // measured 2% faster than the bare barrier, r05nf)
-  std::string s = g_fence ? R"(
+  // read after a write sees it without waiting for the write; only the compiler must not move accesses across:
+  // wavefront-scope release / acquire fences, which wait for the outstanding LDS accesses (measured 2% faster than a
+  // bare barrier with a compiler memory clobber, r05nf)
+  std::string s = R"(
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-)" : R"(
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("" ::: "memory");
-}
 )";
-  if (g_fact) {   // PM_ES_FACT: the four Mendelian children of parent pair e = i * 10 + j (bytes), and the pair (x x, y y)
-                  // whose only child is genotype m (its T10dn row is M's row m)
-    auto gi = [](int b1, int b2) { return b1 < b2 ? (b1 - 1) * (10 - b1) / 2 + (b2 - b1) : (b2 - 1) * (10 - b2) / 2 + (b1 - b2); };
-    int al[10][2], at = 0;
-    for (int x = 1; x <= 4; x++)
-      for (int y = x; y <= 4; y++) { al[gi(x, y)][0] = x; al[gi(x, y)][1] = y; at++; }
-    s += "__device__ const unsigned kMend[100] = {";
-    for (int i = 0; i < 10; i++)
-      for (int j = 0; j < 10; j++) {
-        const int c[4] = {gi(al[i][0], al[j][0]), gi(al[i][0], al[j][1]), gi(al[i][1], al[j][0]), gi(al[i][1], al[j][1])};
-        s += std::to_string((unsigned)c[0] | (unsigned)c[1] << 8 | (unsigned)c[2] << 16 | (unsigned)c[3] << 24) + "u,";
-      }
-    s += "};\n__device__ const int kMrow[10] = {";
-    for (int m = 0; m < 10; m++) s += std::to_string(gi(al[m][0], al[m][0]) * 10 + gi(al[m][1], al[m][1])) + ",";
-    s += "};\n";
-    (void)at;
-  }
   s += "__device__ __forceinline__ int shape_n(int sig) {\n  switch (sig) {\n";
   for (size_t i = 0; i < shape_ns.size(); i++) s += "    case " + std::to_string(i) + ": return " + std::to_string(shape_ns[i]) + ";\n";
   s += "  }\n  return 0;\n}\n";
   std::string k = R"(
-extern "C" __global__ void __launch_bounds__(64 * WPB) WPEU es_hoist_wave(Args A) {   // blockDim = 64 WPB
+extern "C" __global__ void __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4))) es_hoist_wave(Args A) {   // blockDim = 64 WPB
   __shared__ double lk[256], tb[6 * 27];
   __shared__ double ws[WPB][FPW * (WSIZE + PENSZ)];
   for (int i = threadIdx.x; i < 256; i += blockDim.x) lk[i] = A.lktab[i];
@@ -1615,7 +1428,7 @@ T3FILL  __syncthreads();
   // XCD-aware unit order: blocks are dealt round-robin over the 8 XCDs, so the units of one round are split into 8
   // contiguous ranges, one per XCD -- a task's family units (one site's penetrance rows) stay in one XCD's L2
   const long long stride = (long long)gridDim.x * WPB;
-  const long long u_first = (XCD && gridDim.x % 8 == 0)
+  const long long u_first = (true && gridDim.x % 8 == 0)
       ? (long long)(blockIdx.x % 8) * (gridDim.x / 8) * WPB + (long long)(blockIdx.x / 8) * WPB + wave
       : (long long)blockIdx.x * WPB + wave;
   load_items(u_first, c_item);
@@ -1632,7 +1445,7 @@ T3FILL  __syncthreads();
       load_refs(n1_item, n1_ref);
       load_items(u + 2 * stride, n2_item);
     }
-    // (PAIR: the unit's half -- per lane; both halves share the pair's shape)
+    // (true: the unit's half -- per lane; both halves share the pair's shape)
     int leaf_site = -1, pen_site = -1;
     unsigned long long tq = PROF ? __builtin_readcyclecounter() : 0;
     for (int t = 0; t < G; t++) {
@@ -1681,7 +1494,7 @@ PARTS3        }
         PCLK(1);
         continue;
       }
-      if (MULTI && t + 3 <= G && it + 2 < nItems) {   // the site's three 10-state items at once (lanes over item x state)
+      if (false && t + 3 <= G && it + 2 < nItems) {   // the site's three 10-state items at once (lanes over item x state)
         const int ib = __builtin_amdgcn_readfirstlane(A.items[it + 1]), ic = __builtin_amdgcn_readfirstlane(A.items[it + 2]);
         if ((ib >> 3) == site && (ic >> 3) == site && (ib & 7) != 0 && (ib & 7) != 7 && (ic & 7) != 0 && (ic & 7) != 7) {
           int b1, b2, c1, c2;
@@ -1691,7 +1504,7 @@ PARTS3        }
                     G22 = g22 | gi(b2, b2) << 8 | gi(c2, c2) << 16;
           const size_t ostr = (size_t)A.max_ext * A.dcap * A.T;
           switch (sig) {
-PARTS4          }
+          }
           PCLK(3);
           t += 2;
           continue;
@@ -1705,30 +1518,27 @@ PARTS2      }
     leaf_site = -1;   // (the other variants' layouts overlay the leaf prefix's partials)
     switch (sig * 3 + (top ? 2 : dn ? 1 : 0)) {
 )";
-  k.replace(k.find("T3FILL"), 6, g_t3z ? "  for (int i = threadIdx.x; i < 330; i += blockDim.x) {\n    if (i < 320) t3z[i] = kT3z[i];\n"
-                                         "    else t3n[i - 320] = kT3n[i - 320];\n  }\n" : "");
-  for (size_t at; (at = k.find("WSIZE")) != std::string::npos;) k.replace(at, 5, std::to_string(ws));
-  for (size_t at; (at = k.find("PENSZ")) != std::string::npos;) k.replace(at, 5, std::to_string(pensz));
-  for (size_t at; (at = k.find("NPF")) != std::string::npos;) k.replace(at, 3, std::to_string(npf));
-  for (size_t at; (at = k.find("LPF")) != std::string::npos;) k.replace(at, 3, std::to_string(g_wl));
-  for (size_t at; (at = k.find("PAIR")) != std::string::npos;) k.replace(at, 4, g_pair ? "true" : "false");
-  for (size_t at; (at = k.find("FPW")) != std::string::npos;) k.replace(at, 3, std::to_string(g_fpw));
-  k.replace(k.find("XCD &&"), 3, g_xcd ? "true" : "false");
+  auto subst = [](std::string& text, const std::string& token, const std::string& value) {   // every occurrence
+    for (size_t at; (at = text.find(token)) != std::string::npos;) text.replace(at, token.size(), value);
+  };
+  k.replace(k.find("T3FILL"), 6, uses_t3z ? "  for (int i = threadIdx.x; i < 330; i += blockDim.x) {\n    if (i < 320) t3z[i] = kT3z[i];\n"
+                                            "    else t3n[i - 320] = kT3n[i - 320];\n  }\n" : "");
+  subst(k, "WSIZE", std::to_string(ws));
+  subst(k, "PENSZ", std::to_string(pensz));
+  subst(k, "NPF", std::to_string(npf));
+  subst(k, "LPF", std::to_string(kWl));
+  subst(k, "FPW", std::to_string(kFpw));
   {
     std::string cases;
     for (size_t i = 0; i < pens.size(); i++) cases += "        case " + std::to_string(i) + ": " + pens[i] + "(pl, A.np, p0, lk, PEN, lane); break;\n";
     k.replace(k.find("PENS"), 4, cases);
   }
-  for (size_t at; (at = k.find("WPB")) != std::string::npos;) k.replace(at, 3, std::to_string(wpb));
-  k.replace(k.find("MULTI"), 5, pps == 4 ? "true" : "false");
+  subst(k, "WPB", std::to_string(wpb));
   k.replace(k.find("PARTS_ONLY"), 10, parts_only ? "true" : "false");
-  k.replace(k.find("WPEU"), 4, "__attribute__((amdgpu_waves_per_eu(4)))");   // (<= 128 VGPRs: 4 waves per SIMD)
   const std::string call = "(pl, A.np, P11, P12, P22, p0, g11, g12, g22, lk, t10, t10dn, tb, tr0, tr1, W, lane, out, A.T, A.dcap, 0, PEN); break;\n";
-  const std::string call3 = "(pl, A.np, P11, P12, P22, p0, G11, G12, G22, lk, t10, t10dn, tb, tr0, tr1, W, lane, out, A.T, A.dcap, ostr, PEN); break;\n";
-  for (int p = 1; p <= 4; p++) {
+  for (int p = 1; p <= 3; p++) {
     std::string cases;
-    for (size_t i = 0; p <= pps && pps * i + p - 1 < parts.size(); i++)
-      cases += "        case " + std::to_string(i) + ": " + parts[pps * i + p - 1] + (p == 4 ? call3 : call);
+    for (size_t i = 0; 3 * i + p - 1 < parts.size(); i++) cases += "        case " + std::to_string(i) + ": " + parts[3 * i + p - 1] + call;
     const std::string key = "PARTS" + std::to_string(p);
     k.replace(k.find(key), key.size(), cases);
   }
@@ -1736,7 +1546,7 @@ PARTS2      }
   for (size_t i = 0; i < fns.size(); i++)
     if (!fns[i].empty()) s += "      case " + std::to_string(i) + ": " + fns[i] + call;
   s += "    }\n    PCLK(4);\n    }\n  }\n  if (PROF && lane == 0)\n    for (int c = 0; c < 5; c++) atomicAdd(A.prof + c, pc[c]);\n}\n";
-  for (size_t at; (at = s.find("PROF")) != std::string::npos;) s.replace(at, 4, g_prof ? "true" : "false");
+  subst(s, "PROF", opt.prof ? "true" : "false");
   return s;
 }
 
@@ -1789,50 +1599,14 @@ std::string generate(int chrom, const std::vector<Family>& fams, const double (*
   std::vector<std::string> names, bodies, post_names, post_bodies, wave_names, wave_bodies, part_names, pen_names;
   int pensz = 1;
   std::vector<int> shape_ns;   // persons per shape
-  // --denovo, PM_ES_MULTI=1: a grouped task's three 10-state items in one pass of the wave (the default: one after the other;
-  // the three copies of the workspace cut the waves per CU from 14 to 6, and the kernel takes 1.95 ms instead of 1.16)
-  const char* em = getenv("PM_ES_MULTI");
-  const int pps = (em && em[0] == '1') ? 4 : 3;
-  const char* etr = getenv("PM_ES_TR");
-  g_tr_regs = etr && !strcmp(etr, "reg");
-  const char* epf = getenv("PM_ES_PROF");
-  g_prof = epf && epf[0] == '1';
-  const char* epk = getenv("PM_ES_PACK");
-  g_pack = !(epk && epk[0] == '0');
-  const char* erp = getenv("PM_ES_REGP");
-  g_regp = erp ? atoi(erp) : 2;
-  const char* erf = getenv("PM_ES_REGF");
-  g_regf = !(erf && erf[0] == '0');
-  const char* eex = getenv("PM_ES_EXPT");
-  g_expt = eex ? atoi(eex) : 0;
-  const char* efc = getenv("PM_ES_FACT");
-  g_fact = denovo != 0 && efc && efc[0] == '1';
-  const char* epr = getenv("PM_ES_PAIR");
-  const char* efw = getenv("PM_ES_FPW");
-  g_fpw = (denovo != 0 && !(epr && epr[0] == '0') && pps == 3) ? 2 : 1;
-  if (g_fpw > 1 && efw) g_fpw = atoi(efw) >= 4 ? 4 : atoi(efw) >= 2 ? 2 : 1;
-  g_pair = g_fpw > 1;
-  g_wl = 64 / g_fpw;
-  const char* epp = getenv("PM_ES_PENP");
-  g_no_penp = epp && epp[0] == '0';
-  const char* efn = getenv("PM_ES_FENCE");
-  g_fence = !(efn && efn[0] == '0');
-  const char* exd = getenv("PM_ES_XCD");
-  g_xcd = !(exd && exd[0] == '0');
-  const char* ewp = getenv("PM_ES_WSPACK");
-  g_wspack = !(ewp && ewp[0] == '0');
-  const char* etz = getenv("PM_ES_T3Z");
-  g_no_t3z = etz && etz[0] == '0';
-  g_t3z = false;
-  if (g_pair) { g_regp = 0; g_regf = false; g_tr_regs = false; }   // (cross-lane reads by LDS only in pair mode)
-  {
-    int nmax = 0;
-    for (const Family& F : fams) nmax = std::max(nmax, F.n);
-    const char* ebp = getenv("PM_ES_BAPF");
-    // (opt-in, PM_ES_BAPF=1: measured slower, 0.105 vs 0.079 ms per config-4 launch -- 132 VGPRs, 3 waves per SIMD
-    // instead of 4, r05bp)
-    g_bapf = (!denovo && nmax <= 12 && ebp && ebp[0] == '1') ? 3 * nmax : 0;
-  }
+  auto env_is = [](const char* name, char c) { const char* v = getenv(name); return v && v[0] == c; };
+  Opts opt;
+  opt.prof = env_is("PM_ES_PROF", '1');
+  opt.sp3 = !env_is("PM_ES_SP3", '0');
+  opt.t3z = !env_is("PM_ES_T3Z", '0');
+  opt.layout = getenv("PM_JIT_LAYOUT") != nullptr;
+  opt.steps = getenv("PM_JIT_STEPS") != nullptr;
+  bool uses_t3z = false;   // some family of the kernel reads the Mendelian LDS list (emit_type3_dense)
   int ws = 1;
   std::vector<std::pair<int, int>> order;   // (shape, index into fams)
   for (size_t i = 0; i < fams.size(); i++) {
@@ -1854,22 +1628,20 @@ std::string generate(int chrom, const std::vector<Family>& fams, const double (*
         wave_bodies.push_back(gen_pen_fill(fams[i].n, pen_names.back()));
         pensz = std::max(pensz, 10 * fams[i].n);
         for (int v = 0; v < 3; v++) {
-          int w = 0;
           if (denovo == 2 && v > 0) {   // (grouped tasks only: the de novo items go through the parts)
             wave_names.push_back("");
             continue;
           }
           wave_names.push_back("wfam" + std::to_string(id) + "_" + std::to_string(v));
-          wave_bodies.push_back(gen_wave_family(fams[i], chrom, v == 0 ? 3 : 10, v == 2, wave_names.back(), &w, &o3[v]));
-          ws = std::max(ws, w);
+          const WaveFamily A = analyse_wave_family(fams[i], chrom, v == 0 ? 3 : 10, v == 2, wave_names.back(), 0, opt);
+          wave_bodies.push_back(emit_wave_family(A, opt, &o3[v], &uses_t3z));
+          ws = std::max(ws, A.ws);
         }
-        for (int p = 1; p <= pps; p++) {   // the leaf prefix, the 10-state rest, the top rest, the 3-item rest (grouped tasks)
-          int w = 0;
-          double o = 0;
-          part_names.push_back("wfam" + std::to_string(id) + (p == 1 ? "_leaf" : p == 2 ? "_rest" : p == 3 ? "_toprest" : "_rest3"));
-          wave_bodies.push_back(gen_wave_family(fams[i], chrom, 10, p == 3, part_names.back(), &w, p < 4 ? &o3[2 + p] : &o, p == 1 ? 1 : 2,
-                                                p == 4 ? 3 : 1));
-          ws = std::max(ws, w);
+        for (int p = 1; p <= 3; p++) {   // the leaf prefix, the 10-state rest, the top rest (grouped tasks)
+          part_names.push_back("wfam" + std::to_string(id) + (p == 1 ? "_leaf" : p == 2 ? "_rest" : "_toprest"));
+          const WaveFamily A = analyse_wave_family(fams[i], chrom, 10, p == 3, part_names.back(), p == 1 ? 1 : 2, opt);
+          wave_bodies.push_back(emit_wave_family(A, opt, &o3[2 + p], &uses_t3z));
+          ws = std::max(ws, A.ws);
         }
       }
       for (int v = 0; v < 6; v++) out->shape_ops[v].push_back(o3[v]);
@@ -1883,15 +1655,12 @@ std::string generate(int chrom, const std::vector<Family>& fams, const double (*
     out->slot_sig.push_back(o.first);
     out->slot_p0.push_back(fams[o.second].p0);
   }
-  // PAIR: consecutive slots of one shape form a pair; an odd one out is paired with itself (both halves compute the
-  // same family and store the same values to the same coefficients)
-  // (g_fpw families per wave: consecutive slots of one shape form a unit of g_fpw, a short unit padded with its first slot)
-  out->pair = g_pair;
-  out->fpw = g_fpw;
-  for (size_t i = 0; g_pair && i < out->slot_sig.size();) {
+  // es_hoist_wave: consecutive slots of one shape form a unit of kFpw (a pair); an odd one out is paired with itself
+  // (both halves compute the same family and store the same values to the same coefficients)
+  for (size_t i = 0; denovo && i < out->slot_sig.size();) {
     size_t j = i + 1;
-    while (j < out->slot_sig.size() && (int)(j - i) < g_fpw && out->slot_sig[j] == out->slot_sig[i]) j++;
-    for (int f = 0; f < g_fpw; f++) out->pair_k.push_back((int)(i + f < j ? i + f : i));
+    while (j < out->slot_sig.size() && (int)(j - i) < kFpw && out->slot_sig[j] == out->slot_sig[i]) j++;
+    for (int f = 0; f < kFpw; f++) out->pair_k.push_back((int)(i + f < j ? i + f : i));
     i = j;
   }
   out->n_shapes = (int)names.size();
@@ -1905,34 +1674,33 @@ std::string generate(int chrom, const std::vector<Family>& fams, const double (*
     out->wave = false;
   } else {
     // waves per block: as many workspace slices as fit the 64 KB of static LDS next to the tables
-    const int tables = (256 + 6 * 27) * 8 + (g_t3z ? (320 + 10) * 4 : 0);
+    const int tables = (256 + 6 * 27) * 8 + (uses_t3z ? (320 + 10) * 4 : 0);
     // (one wave per SIMD: the occupancy comes from blocks per CU, build() asks the runtime for them)
-    const int slice = g_fpw * (ws + pensz) * 8;   // (a unit's family slices per wave)
+    const int slice = kFpw * (ws + pensz) * 8;   // (a unit's family slices per wave)
     // (at most 4: one wave per SIMD and block; measured on config 4 --denovo, 4 beat 1, 2, 5 and 6 even where those
     // gave more waves per CU -- profiles/r05k_ab_es_wpb.txt)
     const int fit = (64 * 1024 - tables) / slice;
     out->wpb = std::max(0, std::min(4, fit));
-    if (const char* ew = getenv("PM_ES_WPB")) out->wpb = std::max(1, std::min(fit, atoi(ew)));
     // (wpb 0: a family too large for one slice -- the engine's generic kernel)
-    std::string wk = gen_wave_kernel(wave_names, part_names, pen_names, shape_ns, pps, ws, pensz, std::max(1, out->wpb), denovo == 2);
+    std::string wk = gen_wave_kernel(wave_names, part_names, pen_names, shape_ns, ws, pensz, std::max(1, out->wpb), denovo == 2, uses_t3z, opt);
     const size_t at = wk.find("extern \"C\"");   // device helpers first, then the family functions, then the kernel
     src += wk.substr(0, at);
-    {   // the family units' slot words (unit = slot pair in pair mode, else slot; both halves' entries): constants
-      const size_t nu = g_pair ? out->pair_k.size() / g_fpw : out->slot_e.size();
-      const std::string nf = std::to_string(g_fpw * nu);
+    {   // the family units' slot words (unit = slot pair; both halves' entries): constants
+      const size_t nu = out->pair_k.size() / kFpw;
+      const std::string nf = std::to_string(kFpw * nu);
       std::string p0 = "__constant__ int kUP0[" + nf + "] = {", e = "__constant__ int kUE[" + nf + "] = {",
                   sg = "__constant__ int kUSig[" + std::to_string(nu) + "] = {";
       for (size_t u = 0; u < nu; u++) {
-        for (int f = 0; f < g_fpw; f++) {
-          const int k = g_pair ? out->pair_k[g_fpw * u + f] : (int)u;
+        for (int f = 0; f < kFpw; f++) {
+          const int k = out->pair_k[kFpw * u + f];
           p0 += std::to_string(out->slot_p0[k]) + ",";
           e += std::to_string(out->slot_e[k]) + ",";
         }
-        sg += std::to_string(out->slot_sig[g_pair ? out->pair_k[g_fpw * u] : (int)u]) + ",";
+        sg += std::to_string(out->slot_sig[out->pair_k[kFpw * u]]) + ",";
       }
       src += p0 + "};\n" + e + "};\n" + sg + "};\n__device__ constexpr int kNUnits = " + std::to_string(nu) + ";\n";
     }
-    if (g_t3z) {   // the plain Mendelian T(e = i 10 + j, k)'s non-zero terms per child state k, ascending e: e << 2 | code
+    if (uses_t3z) {   // the plain Mendelian T(e = i 10 + j, k)'s non-zero terms per child state k, ascending e: e << 2 | code
       auto gi = [](int b1, int b2) { return b1 < b2 ? (b1 - 1) * (10 - b1) / 2 + (b2 - b1) : (b2 - 1) * (10 - b2) / 2 + (b1 - b2); };
       std::vector<double> T(1000, 0.0);
       for (int i = 1; i <= 4; i++)
@@ -2029,9 +1797,9 @@ bool build(int device, int chrom, const std::vector<Family>& fams, const double 
     *err = "hipModuleGetFunction of the generated kernels failed";
     return false;
   }
-  if (denovo || g_bapf) {   // resident blocks per CU (VGPRs and LDS): the launch's grid
+  if (denovo) {   // resident blocks per CU (VGPRs and LDS): the launch's grid
     int nb = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, out->fn, denovo ? 64 * out->wpb : 256, 0) != hipSuccess) nb = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, out->fn, 64 * out->wpb, 0) != hipSuccess) nb = 0;
     out->blocks_per_cu = nb;
     if (getenv("PM_JIT_LAYOUT")) fprintf(stderr, "es_hoist_wave: wpb %d ws %d blocks/CU %d\n", out->wpb, out->ws, nb);
   }
@@ -2150,10 +1918,7 @@ struct FusedArgs {
 };
 )";
   for (auto& b : bodies) src += b;
-  const char* wpe = getenv("PM_FUSED_WPE");   // (experiments: amdgpu_waves_per_eu of the kernel)
-  src += std::string("extern \"C\" __global__ void __launch_bounds__(64) ") +
-         (wpe ? "__attribute__((amdgpu_waves_per_eu(" + std::string(wpe) + ", " + std::string(wpe) + "))) " : "") +
-         "ep_brent_jit(FusedArgs A) {\n";
+  src += "extern \"C\" __global__ void __launch_bounds__(64) ep_brent_jit(FusedArgs A) {\n";
   src += R"(  __shared__ double lk[256];
   for (int i = threadIdx.x; i < 256; i += 64) lk[i] = A.lktab[i];
   __syncthreads();

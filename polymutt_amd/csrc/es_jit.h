@@ -67,16 +67,16 @@ struct Kernel {
   std::vector<int> slot_e, slot_sig, slot_p0;   // host copies (the engine uploads them)
   int n_shapes = 0;
   double compile_ms = 0;
-  bool wave = false;         // --denovo: es_hoist_wave, one (item, family) per wave, blockDim = 64 wpb
+  bool wave = false;         // --denovo: es_hoist_wave, one (item, family) per half-wave, blockDim = 64 wpb
   // FP64 operations of one (item, family) hoisting per shape, by variant: 0 bi-allelic, 1 10-state (de novo items),
   // 2 top (the de novo monomorphism item), 3 the leaf prefix of a grouped task, 4 / 5 its 10-state / top rest (3 + 4 ==
   // 1, 3 + 5 == 2); the bi-allelic engines fill variant 0 only
   std::vector<double> shape_ops[6];
   int wpb = 0, ws = 0;       // waves per block, workspace doubles per wave
   int blocks_per_cu = 0;     // es_hoist_wave blocks resident per CU (the runtime's occupancy; 0 unknown)
-  bool pair = false;         // es_hoist_wave hoists two same-shape families per wave, one per half-wave (PM_ES_PAIR)
-  std::vector<int> pair_k;   // [fpw units] slot indices of each unit of fpw same-shape slots (a short unit: its first again)
-  int fpw = 1;               // families per wave (PM_ES_FPW; 2 = the pair mode)
+  // es_hoist_wave hoists two same-shape families per wave, one per half-wave: [2 pairs] the slot indices of each pair of
+  // consecutive same-shape slots (an odd one out: its own index twice)
+  std::vector<int> pair_k;
 };
 
 // The fused Elston-Stewart Brent kernel ep_brent_jit (bi-allelic engines whose every family is peeled: config 4): one wave

@@ -2,7 +2,11 @@
 // device.  Loads a pedigree (.dat/.ped), builds the extended families' hoisting kernel source for every chromosome
 // class as the engine would (slot order of a 64-lane plan), compiles each with hipRTC for gfx950 and prints one
 // line per class: shapes, source bytes, code-object bytes, compile ms.  Exit status 1 on any failure.
-//   jit_check DAT PED [--emit FILE]
+//   jit_check DAT PED [--emit FILE] [--emit-all DIR] [--no-compile]
+// --emit FILE: class 0's sources and code objects (FILE, FILE.dn2, FILE.dn1, FILE.fused, each with .co).
+// --emit-all DIR: the source of every generate() run (DIR/class<c>_dn<0|2|1>.hip) and of every generate_fused() run that
+// yields a kernel (DIR/fused<c>.hip) -- what tests/test_cpu_jit_source.py hashes.
+// --no-compile: skip hipRTC (code 0 in the printed lines): the dump then takes well under a second.
 #include <chrono>
 #include <cstdio>
 #include <string>
@@ -18,7 +22,7 @@ static const double kTBA[5][27] = {   // transmission_BA tables (FamilyLikelihoo
     {1, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 1}};
 
 int main(int argc, char** argv) {
-  if (argc < 3) { fprintf(stderr, "usage: jit_check DAT PED [--emit FILE]\n"); return 2; }
+  if (argc < 3) { fprintf(stderr, "usage: jit_check DAT PED [--emit FILE] [--emit-all DIR] [--no-compile]\n"); return 2; }
   pmhost::Pedigree ped;
   try {
     ped.load(argv[1], argv[2]);
@@ -26,7 +30,20 @@ int main(int argc, char** argv) {
     fprintf(stderr, "pedigree: %s\n", e.what());
     return 1;
   }
-  const std::string emit = argc >= 5 && std::string(argv[3]) == "--emit" ? argv[4] : "";
+  std::string emit, emit_all;
+  bool no_compile = false;
+  for (int a = 3; a < argc; a++) {
+    const std::string o = argv[a];
+    if (o == "--emit" && a + 1 < argc) emit = argv[++a];
+    else if (o == "--emit-all" && a + 1 < argc) emit_all = argv[++a];
+    else if (o == "--no-compile") no_compile = true;
+    else { fprintf(stderr, "jit_check: unknown option %s\n", o.c_str()); return 2; }
+  }
+  auto write_text = [](const std::string& path, const std::string& text) {
+    FILE* fh = fopen(path.c_str(), "w");
+    if (!fh || fputs(text.c_str(), fh) < 0 || fclose(fh) != 0) { fprintf(stderr, "jit_check: cannot write %s\n", path.c_str()); return false; }
+    return true;
+  };
   const pm_pedigree v = ped.view();
   std::vector<pmjit::Family> fams;
   int e = 0;
@@ -51,11 +68,12 @@ int main(int argc, char** argv) {
       FILE* fh = fopen((dn ? emit + ".dn" + std::to_string(dn) : emit).c_str(), "w");
       if (fh) { fputs(src.c_str(), fh); fclose(fh); }
     }
+    if (!emit_all.empty() && !write_text(emit_all + "/class" + std::to_string(cls) + "_dn" + std::to_string(dn) + ".hip", src)) return 1;
     std::vector<char> code;
     std::string err;
     const auto t0 = std::chrono::steady_clock::now();
-    if (!pmjit::compile(src, &code, &err)) { fprintf(stderr, "class %d: %s\n", cls, err.c_str()); return 1; }
-    if (!emit.empty() && cls == 0) {   // the code object too (register and LDS use: llvm-readelf --notes)
+    if (!no_compile && !pmjit::compile(src, &code, &err)) { fprintf(stderr, "class %d: %s\n", cls, err.c_str()); return 1; }
+    if (!emit.empty() && cls == 0 && !no_compile) {   // the code object too (register and LDS use: llvm-readelf --notes)
       FILE* fh = fopen(((dn ? emit + ".dn" + std::to_string(dn) : emit) + ".co").c_str(), "wb");
       if (fh) { fwrite(code.data(), 1, code.size(), fh); fclose(fh); }
     }
@@ -74,10 +92,11 @@ int main(int argc, char** argv) {
       FILE* fh = fopen((emit + ".fused").c_str(), "w");
       if (fh) { fputs(src.c_str(), fh); fclose(fh); }
     }
+    if (!emit_all.empty() && !write_text(emit_all + "/fused" + std::to_string(cls) + ".hip", src)) return 1;
     std::vector<char> code;
     std::string err;
-    if (!pmjit::compile(src, &code, &err)) { fprintf(stderr, "fused class %d: %s\n", cls, err.c_str()); return 1; }
-    if (!emit.empty() && cls == 0) {
+    if (!no_compile && !pmjit::compile(src, &code, &err)) { fprintf(stderr, "fused class %d: %s\n", cls, err.c_str()); return 1; }
+    if (!emit.empty() && cls == 0 && !no_compile) {
       FILE* fh = fopen((emit + ".fused.co").c_str(), "wb");
       if (fh) { fwrite(code.data(), 1, code.size(), fh); fclose(fh); }
     }

@@ -60,7 +60,7 @@ def main():
     summary = {kind: {"occupancy": v["ops"] / v["slots"] if v["slots"] else 0.0, "min": v["min"], "max": v["max"]}
                for kind, v in sorted(kinds.items())}
     out = {"shape": a.shape, "families": a.families, "seed": a.seed,
-           "source": "tests/native/build/jit_check with PM_JIT_LAYOUT=1 (csrc/es_jit.cpp gen_wave_family / gen_family)",
+           "source": "tests/native/build/jit_check with PM_JIT_LAYOUT=1 (csrc/es_jit.cpp emit_wave_family / gen_family)",
            "by_kind": summary, "functions": rows}
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
