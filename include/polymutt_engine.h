@@ -301,6 +301,41 @@ int pm_engine_set_denovo_carriers(pm_engine *eng, int32_t top_k, int32_t want_al
  * without want_all).  After PM_EBRENT only the rows before the stuck site are valid. */
 int pm_engine_denovo_carriers(pm_engine *eng, pm_person_dn *top, pm_person_dn *all);
 
+/* De novo calling from VCF input (vcf_mode engines; additive to ABI 8: callers detect the feature by this symbol; no
+ * reference counterpart -- PedVCF::VarCallFromVCF never calls its _denovo members).  A vcf_mode block carries data in the
+ * three genotypes of (ref, alt) only, so the de novo model collapses to three states.  For a called site of an autosomal
+ * section with alleles (a1, a2) = (ref, alt):
+ *   g            = (g11, g12, g22), the GLF genotype indices of a1a1, a1a2, a2a2;
+ *   M3[x][y]     = M[g[x]][g[y]], M the 10 x 10 genotype mutation matrix (GenotypeMutationModel::SetGenoMutMatrix) of
+ *                  pm_params.denovo_mut_rate / denovo_tstv;
+ *   T            = the autosomal bi-allelic transmission (SetTransmissionMatrix_BA);
+ *   Tdn[i][j][k] = Sum_m T[i][j][m] M3[m][k].
+ * L^dn(f) is the vcf_mode objective (FamilyLikelihoodSeq_VCF::CalcAllFamLogLikelihood, Hardy-Weinberg founder priors in f
+ * everywhere) with the families routed as for varllk[1] -- all-founder families the product of single persons; nuclear
+ * families in closed form when n_fam > 1; everything else, a single nuclear family included, by the bi-allelic peel --
+ * and these differences:
+ *   closed form: each child's factor for the parental pair (i, j) is Sum_k Tdn[i][j][k] l_k (likelihoodONEKid_denovo applied
+ *                to D = M3 l);
+ *   peel:        type-1 steps (offspring -> parents) use Tdn; type-3 steps (parents -> only offspring) use Tdn when the
+ *                couple has no marriage partial yet and plain T when it has one (the reference's 10-state quirk,
+ *                FamilyLikelihoodES.cpp:1391, kept so that the 10-state oracle pins the values); type-2 steps are unchanged.
+ * Outputs per called site: N = max_f log10 L^dn(f) by the same OptimizeFrequency + Brent as every other item, D =
+ * the standard maximum varllk[1], DQ = N - D:  denovo_lr = DQ, varllk[2] = N, varfreq[2] = its maximiser, evals[2] = its
+ * evaluation count.  (The D subtracted is the standard objective at varfreq[1] formed by the de novo kernel with the
+ * log10 it uses for N: varllk[1] up to the rounding of its log10, ~1e-16 absolute, which matters only where both
+ * likelihoods are within 1e-7 of 1.)
+ * n_cfg, maxidx, every other field and the genotype rows are those of the feature-off run, byte for byte.  Only the three
+ * planes g11, g12, g22 of the block are read.  A de novo Brent that hits ITMAX is a stuck site like the standard one:
+ * PM_EBRENT, pm_engine_stuck_site = the first site at which either stuck.
+ * Not in the model: chrX/Y/MT sections (the autosomal transmission is wrong there: no DQ is computed, the results are
+ * those of the feature-off run); indel records (the engine cannot tell them from SNVs: the host prints no tag for them);
+ * the fixed single-trio prior of the GLF path (it gives two homozygous-reference parents weight 0, hiding exactly the
+ * event looked for).
+ * on = 0 (the default): nothing is allocated or launched, every output byte is that of an engine without the feature.
+ * PM_EINVAL: an engine without vcf_mode, or a submitted batch not yet collected.  pm_engine_set_denovo_families and
+ * pm_engine_set_denovo_carriers keep refusing vcf_mode engines. */
+int pm_engine_set_vcf_denovo(pm_engine *eng, int32_t on);
+
 /* Page-locked host memory for pm_engine_submit's inputs and the result rows (H2D/D2H at full PCIe rate). */
 int pm_host_alloc(uint64_t bytes, void **h_ptr);
 int pm_host_free(void *h_ptr);

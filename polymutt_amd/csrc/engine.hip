@@ -3,6 +3,7 @@
 // separate units (brent_inst.hip, one object per PM_BRENT_PART) and declared extern here (brent_variants.h).
 #include "engine_dev.h"
 #include "brent_variants.h"
+#include "vcf_denovo_dev.h"
 
 #define PM_BRENT_X(part, ...) extern template __global__ void k_brent<__VA_ARGS__>(DevArgs, int);
 PM_BRENT_VARIANTS
@@ -118,6 +119,12 @@ struct pm_engine {
   int2* d_pdn_kids = nullptr;       // the non-founders {family, member}: nuclear families' in fam_perm order, then extended families'
   int8_t* d_pdn_is_kid = nullptr;   // [n_person]
   double* d_pdn_jbuf = nullptr;     // [pdn_grid][pdn_n_es * 111] clamped-peel values of k_person_dn<true>
+  // de novo calling from VCF input (pm_engine_set_vcf_denovo): off = no buffer, no launch
+  bool vdn_on = false;
+  int vdn_T = 0, vdn_grid = 0, vdn_terms = 0, vdn_peel = 0, vdn_nuc = 0;
+  size_t vdn_lds = 0;        // dynamic LDS of k_vdn_brent (the hoisted coefficients), 0: they live in d_vdn_co
+  int* d_vdn_terms = nullptr;
+  double *d_vdn_co = nullptr, *d_vdn_ws = nullptr;
   std::vector<int> fam_kind_h, fam_perm_h;
   std::vector<int32_t> fa_h, mo_h;  // family-local parent indices (-1: none)
   unsigned long long* d_counters = nullptr;
@@ -328,7 +335,8 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_pl, E->d_stage, E->d_ref, E->d_dm, E->d_res, E->d_calls, E->d_raw, E->d_minv, E->d_mono, E->d_evals,
                   E->d_items[0], E->d_items[1], E->d_items[2], E->d_counts, E->d_eval_total, E->d_row_site,
                   E->d_counters, E->d_row_blk, E->d_qctr, E->d_fam_top, E->d_fam_sum, E->d_fam_all, E->d_fam_line,
-                  E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf};
+                  E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf,
+                  E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws};
   for (void* b : bufs) if (b) hipFree(b);
   for (auto& pl : E->d_jit_slots)
     for (int* b : pl) if (b) hipFree(b);
@@ -1238,6 +1246,26 @@ static int launch_brent(pm_engine* E, const DevArgs& A0, int list, bool unrelate
   return PM_OK;
 }
 
+// The de novo Brent item of every called site of a vcf_mode batch (three-genotype mutation model, vcf_denovo_dev.h) and the
+// four result fields it fills; timed with the Brent launches (pm_kernel_stats).
+static int launch_vcf_denovo(pm_engine* E, const DevArgs& A) {
+  VdnArgs V;
+  V.terms = E->d_vdn_terms; V.n_terms = E->vdn_terms; V.n_peel = E->vdn_peel; V.n_nuc = E->vdn_nuc;
+  V.co_lds = E->vdn_lds > 0; V.co = E->d_vdn_co; V.ws = E->d_vdn_ws;
+  const int grid = std::max(1, std::min(E->vdn_grid, A.n));
+  hipEvent_t a, b;
+  HIP_TRY(hipEventCreate(&a));
+  HIP_TRY(hipEventCreate(&b));
+  E->brent_events.push_back({a, b});
+  HIP_TRY(hipEventRecord(a, E->stream));
+  hipLaunchKernelGGL(E->vdn_T == 64 ? k_vdn_brent<64> : k_vdn_brent<256>, dim3(grid), dim3(E->vdn_T), E->vdn_lds, E->stream, A, V);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(b, E->stream));
+  hipLaunchKernelGGL(k_finalize_vdn, dim3((A.n + 255) / 256), dim3(256), 0, E->stream, A);
+  HIP_TRY(hipGetLastError());
+  return PM_OK;
+}
+
 static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* dm, const uint8_t* ref, pm_site_result* res,
                         pm_geno_call* calls) {
   DevArgs A = make_args(E, n, pl, dm, ref, res, calls);
@@ -1283,6 +1311,7 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
   if (E->vcf) {
     hipLaunchKernelGGL(k_finalize_vcf, dim3(gb), dim3(tb), 0, E->stream, A);
     HIP_TRY(hipGetLastError());
+    if (E->vdn_on && E->chrom == PM_CHR_AUTO && (rc = launch_vcf_denovo(E, A))) return rc;
   } else {
     hipLaunchKernelGGL(k_select, dim3(gb), dim3(tb), 0, E->stream, A);
     HIP_TRY(hipGetLastError());
@@ -1446,6 +1475,57 @@ int pm_engine_set_denovo_families(pm_engine* E, int32_t top_k, int32_t want_all)
   else rc = dalloc(&E->d_fam_line, (size_t)E->fam_grid * nf);
   if (rc) return rc;
   E->fam_top_k = top_k;
+  return PM_OK;
+}
+
+int pm_engine_set_vcf_denovo(pm_engine* E, int32_t on) {
+  if (!E) { pm_set_last_error("pm_engine_set_vcf_denovo: invalid arguments"); return PM_EINVAL; }
+  if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_denovo: the engine was created without vcf_mode"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_vcf_denovo: a submitted batch has not been collected"); return PM_EINVAL; }
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  E->vdn_on = false;
+  void** bufs[] = {(void**)&E->d_vdn_terms, (void**)&E->d_vdn_co, (void**)&E->d_vdn_ws};
+  for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+  if (!on) return PM_OK;
+  // the objective's terms, routed like the vcf_mode objective: peeled families (every family with offspring when the
+  // pedigree is one family, the extended ones otherwise), nuclear families in closed form, founder persons
+  std::vector<int> peel, nuc, pers;
+  for (int f = 0; f < E->n_fam; f++) {
+    const int kind = E->fam_kind_h[f];
+    if (kind == PM_FAM_FOUNDERS) for (int p = E->fam_start_h[f]; p < E->fam_start_h[f + 1]; p++) pers.push_back(p);
+    else if (kind == PM_FAM_NUCLEAR && E->n_fam > 1) nuc.push_back(f);
+    else {
+      if (E->peel_start_h[f + 1] == E->peel_start_h[f]) {
+        pm_set_last_error("pm_engine_set_vcf_denovo: a family with offspring has no peeling schedule (pm_pedigree.steps)");
+        return PM_EPED;
+      }
+      peel.push_back(f);
+    }
+  }
+  E->vdn_peel = (int)peel.size(); E->vdn_nuc = (int)nuc.size();
+  std::vector<int> terms(peel);
+  terms.insert(terms.end(), nuc.begin(), nuc.end());
+  terms.insert(terms.end(), pers.begin(), pers.end());
+  E->vdn_terms = (int)terms.size();
+  E->vdn_T = E->vdn_terms <= 128 ? 64 : 256;
+  // coefficients in LDS when a block's fit (<= 96 KB); blocks per CU from the LDS budget, at most 16 waves per CU
+  const size_t co_bytes = (size_t)5 * (terms.size() - peel.size()) * sizeof(double);
+  E->vdn_lds = co_bytes <= 96 * 1024 ? std::max<size_t>(co_bytes, 8) : 0;
+  const void* fn = E->vdn_T == 64 ? (const void*)k_vdn_brent<64> : (const void*)k_vdn_brent<256>;
+  if (E->vdn_lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)E->vdn_lds));
+  int bpc = std::max(1, std::min(1024 / E->vdn_T, (int)((160 * 1024) / (E->vdn_lds + 4 * 1024))));
+  E->vdn_grid = E->n_cu * bpc;
+  const size_t ws_block = (size_t)E->ws_per_lane * E->vdn_T * sizeof(double), co_block = E->vdn_lds ? 0 : co_bytes;
+  if (ws_block + co_block > 0)   // workspace and spilled coefficients: <= 1 GiB, never below one block
+    E->vdn_grid = (int)std::max<size_t>(1, std::min<size_t>(E->vdn_grid, ((size_t)1 << 30) / (ws_block + co_block)));
+  E->vdn_grid = std::min(E->vdn_grid, E->max_batch);
+  int rc;
+  if ((rc = dalloc(&E->d_vdn_terms, terms.size())) || (rc = dalloc(&E->d_vdn_ws, (size_t)E->vdn_grid * E->ws_per_lane * E->vdn_T)) ||
+      (rc = dalloc(&E->d_vdn_co, (size_t)E->vdn_grid * co_block / sizeof(double))))
+    return rc;
+  HIP_TRY(hipMemcpy(E->d_vdn_terms, terms.data(), sizeof(int) * terms.size(), hipMemcpyHostToDevice));
+  E->vdn_on = true;
   return PM_OK;
 }
 

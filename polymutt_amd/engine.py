@@ -125,6 +125,7 @@ EXPORTS = {
     "pm_engine_denovo_rows": (i32, [C.c_void_p, P(i32)]),
     "pm_engine_set_denovo_carriers": (i32, [C.c_void_p, i32, i32]),
     "pm_engine_denovo_carriers": (i32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pm_engine_set_vcf_denovo": (i32, [C.c_void_p, i32]),
     "pm_host_alloc": (i32, [u64, P(C.c_void_p)]),
     "pm_host_free": (i32, [C.c_void_p]),
     "pm_engine_to_planar": (i32, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
@@ -401,6 +402,12 @@ class Engine:
         full = np.zeros((rows, self.n_person), dtype=PERSON_DN_DTYPE) if self._pdn_all else None
         self._check(self.lib.pm_engine_denovo_carriers(self.h, _ptr(top), None if full is None else _ptr(full)))
         return top, full
+
+    def set_vcf_denovo(self, on=True):
+        """pm_engine_set_vcf_denovo (vcf_mode engines): every called autosomal site also gets the maximum N of the
+        three-genotype de novo model in varllk[2] (maximiser varfreq[2], evaluations evals[2]) and DQ = N - varllk[1] in
+        denovo_lr; off (the default) leaves every output byte as it was."""
+        self._check(self.lib.pm_engine_set_vcf_denovo(self.h, 1 if on else 0))
 
     def stuck_site(self):
         """pm_engine_stuck_site: the first site of the last finished batch whose Brent hit ITMAX (-1: none)."""

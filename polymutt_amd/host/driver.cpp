@@ -49,6 +49,7 @@ Options parse_command_line(int argc, char** argv) {
       {"gpu", 'i', &o.device}, {"batch", 'i', &o.batch}, {"io_threads", 'i', &o.io_threads}, {"engines", 'i', &o.engines},
       {"in_blocks", 's', &o.blocksIn}, {"glf2blocks", 's', &o.blocksOut}, {"block_sites", 'i', &o.blockSites}, {"exact_log10", 'b', &o.exact_log10}, {"numerics", 's', &o.numerics},
       {"denovo_families", 'i', &o.denovo_families}, {"denovo_carriers", 'i', &o.denovo_carriers},
+      {"vcf_denovo", 'b', &o.vcf_denovo},
   };
   auto assign = [](Flag& f, const char* v) {
     switch (f.kind) {
@@ -98,6 +99,7 @@ Options parse_command_line(int argc, char** argv) {
     if (!o.vcfInFile.empty()) throw FatalError("--denovo_families is not available with --in_vcf\n");
     if (o.denovo_families < 1 || o.denovo_families > 8) throw FatalError("--denovo_families takes a family count from 1 to 8\n");
   }
+  if (o.vcf_denovo && o.vcfInFile.empty()) throw FatalError("--vcf_denovo needs --in_vcf\n");
   if (o.denovo_carriers_given) {
     if (!o.denovo) throw FatalError("--denovo_carriers needs --denovo\n");
     if (!o.vcfInFile.empty()) throw FatalError("--denovo_carriers is not available with --in_vcf\n");

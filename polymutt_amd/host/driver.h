@@ -32,6 +32,9 @@ struct Options {
   // their posterior and most likely event (INFO tags DNC / DNCP / DNCE)
   int denovo_carriers = 0;
   bool denovo_carriers_given = false;
+  // --vcf_denovo (with --in_vcf): biallelic autosomal SNV records whose three-genotype de novo model beats the standard
+  // one by DQ >= --minLLR_denovo get ;DQ= after DP= (pm_engine_set_vcf_denovo; --rate_denovo, --tstv_denovo apply)
+  bool vcf_denovo = false;
   std::string cmd;
   pm_params params() const;
 };
@@ -83,6 +86,8 @@ class SiteEvaluator {
   // --denovo_carriers: the same protocol with the rows [rows][K] of ranked non-founders
   virtual void set_denovo_carriers(int top_k) { (void)top_k; throw FatalError("--denovo_carriers needs the GPU engine\n"); }
   virtual void denovo_carriers(pm_person_dn* top) { (void)top; throw FatalError("--denovo_carriers needs the GPU engine\n"); }
+  // --vcf_denovo: once, before the first batch; the results then carry DQ in denovo_lr (pm_engine_set_vcf_denovo)
+  virtual void set_vcf_denovo(bool on) { (void)on; throw FatalError("--vcf_denovo is not supported by this evaluator\n"); }
   // Host memory for the batch buffers (the engine: page-locked, for asynchronous copies)
   virtual void* host_alloc(size_t bytes);
   virtual void host_free(void* p);

@@ -115,6 +115,9 @@ class EngineEvaluator : public SiteEvaluator {
     if (!last_) throw FatalError("GPU engine error: no finished batch\n");
     check(pm_engine_denovo_carriers(last_, top, nullptr));
   }
+  void set_vcf_denovo(bool on) override {
+    for (auto* e : eng_) check(pm_engine_set_vcf_denovo(e, on ? 1 : 0));
+  }
   void* host_alloc(size_t bytes) override {
     void* p = nullptr;
     if (pm_host_alloc(bytes ? bytes : 1, &p) != PM_OK || !p) return SiteEvaluator::host_alloc(bytes);   // pageable fallback

@@ -339,7 +339,12 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
             "##FILTER=<ID=LOWDP,Description=\"Low Depth filter when the average depth per sample is lessn than 1\">\n"
             "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Total Read Depth\">\n"
             "##INFO=<ID=AF,Number=A,Type=Float,Description=\"Alternative Allele Frequency\">\n"
-            "##INFO=<ID=AC,Number=1,Type=Integer,Description=\"Alternative Allele Count\">\n"
+            "##INFO=<ID=AC,Number=1,Type=Integer,Description=\"Alternative Allele Count\">\n");
+    if (opt.vcf_denovo)   // (--vcf_denovo: no reference counterpart)
+      fprintf(out, "%s",
+              "##INFO=<ID=DQ,Number=1,Type=Float,Description=\"De Novo Mutation Quality: log10 likelihood ratio of the de novo "
+              "mutation model and the standard model\">\n");
+    fprintf(out, "%s",
             "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
             "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype Quality\">\n"
             "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Read Depth\">\n"
@@ -359,6 +364,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   prior *= opt.theta;
   const double tstv = 2.0, prior_ts = tstv / (tstv + 1), prior_tv = 0.5 / (tstv + 1);
 
+  if (opt.vcf_denovo) eval.set_vcf_denovo(true);
   const int B = std::max(1, opt.batch);
   // Two batches: the main thread reads, classifies and parses records into one while the flusher thread runs the
   // engine on the other, formats its records and hands their text to the writer thread.  A batch's PL rows are in
@@ -406,7 +412,8 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
 
   // The state a record is printed with: its own (a computed record) or the previous computed record's (a record
   // without data, PedVCF.cpp:113-122): QUAL, the AF minimiser and every person's call.
-  struct RecState { double qual, min; const pm_vcf_call* calls; };
+  // dq (--vcf_denovo): the record's own DQ tag; never carried to a record without data
+  struct RecState { double qual, min; const pm_vcf_call* calls; bool has_dq = false; double dq = 0.0; };
   auto fresh_state = [&](const Pending& r, const pm_site_result* Rs, const pm_vcf_call* C) {
     // mono/poly -> QUAL (PedVCF.cpp:136-152), with the reference's operator-precedence slip
     const double mono = Rs->varllk[0], poly = Rs->varllk[1];
@@ -426,6 +433,9 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     }
     S.min = Rs->af;
     S.calls = C;
+    // DQ: biallelic SNV records of an autosome (evals[2] > 0: the engine ran the de novo model) at or above the threshold
+    S.has_dq = opt.vcf_denovo && !r.indel && Rs->evals[2] > 0 && Rs->denovo_lr >= opt.denovo_llr;
+    S.dq = Rs->denovo_lr;
     return S;
   };
   // OutputVCF (FamilyLikelihoodSeq_VCF.cpp:412-521): one record's text into `out` (no shared state: the records of a
@@ -481,8 +491,10 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     if (hn >= (int)sizeof(head)) { putf(hn); w += snprintf(w, (size_t)hn + 1, "\t%.2f\t", S.qual); } else putf(hn);
     fld(6);
     const char* fmt_s = fs.PL_idx > 0 ? "GT:GQ:DP:PL" : "GT:GQ:DP:GL";
-    hn = snprintf(head, sizeof(head), "\tAF=%.2f;AC=%d;DP=%d\t%s", 1 - S.min, AC, totalDepth, fmt_s);
-    if (hn >= (int)sizeof(head)) { putf(hn); w += snprintf(w, (size_t)hn + 1, "\tAF=%.2f;AC=%d;DP=%d\t%s", 1 - S.min, AC, totalDepth, fmt_s); }
+    char dq_s[64] = "";
+    if (S.has_dq) snprintf(dq_s, sizeof(dq_s), ";DQ=%.3f", S.dq);
+    hn = snprintf(head, sizeof(head), "\tAF=%.2f;AC=%d;DP=%d%s\t%s", 1 - S.min, AC, totalDepth, dq_s, fmt_s);
+    if (hn >= (int)sizeof(head)) { putf(hn); w += snprintf(w, (size_t)hn + 1, "\tAF=%.2f;AC=%d;DP=%d%s\t%s", 1 - S.min, AC, totalDepth, dq_s, fmt_s); }
     else putf(hn);
     for (size_t s = 0; s < ns; s++) {
       const pm_vcf_call& c = S.calls[inc_cols[s].second];
@@ -577,6 +589,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     for (size_t k = 0; k < npend; k++) {
       const Pending& r = *pend[k];
       if (r.computed) cur = fresh_state(r, &bb.res[r.slot], calls + (size_t)bb.res[r.slot].call_row * np);
+      else cur.has_dq = false;
       states[k] = cur;
     }
     std::vector<std::string>& T = texts[tcur];
