@@ -99,8 +99,10 @@ typedef struct {
                                   no filters; res.varllk[0] = mono, varllk[1] = poly (no priors), af = minimiser */
 } pm_params;
 
-/* Diagnostic environment variables read by pm_engine_create / pm_engine_run (tests and tools only; results
- * never depend on them beyond the documented bit-identical alternatives):
+/* Diagnostic environment variables (tests and tools only; results never depend on them beyond the documented
+ * bit-identical alternatives).  The engine reads every one of its switches once, at pm_engine_create, and keeps the
+ * values for the engine's life (EngineSwitches in polymutt_amd/csrc/brent_plan.h lists them all; INTEGRATION.md
+ * describes them); setting or clearing one afterwards does not affect a live engine.  Among them:
  *   PM_NO_PREFETCH=1  the lean kernels hoist from direct HBM loads instead of LDS-staged PL bytes (tests
  *                     compare the two paths bit for bit);
  *   PM_BRENT_TS=T,S   force the Brent lane plan to T threads x S slots when it holds the pedigree

@@ -1,13 +1,22 @@
 // engine.hip -- host side of the MI355X (gfx950) engine (pm_engine_*, the C ABI of include/polymutt_engine.h) and the
 // non-Brent kernels' instantiations.  The device code is in engine_dev.h; the k_brent instantiations are compiled in
-// separate units (brent_inst.hip, one object per PM_BRENT_PART) and declared extern here (brent_variants.h).
+// separate units (brent_inst.hip, one object per PM_BRENT_PART) and declared extern here (brent_variants.h).  Which of
+// them a launch takes is decided in brent_plan.h (host-only) and resolved through kBrentTable.
 #include "engine_dev.h"
+#include "brent_plan.h"
 #include "brent_variants.h"
 #include "vcf_denovo_dev.h"
 
 #define PM_BRENT_X(part, ...) extern template __global__ void k_brent<__VA_ARGS__>(DevArgs, int);
 PM_BRENT_VARIANTS
 #undef PM_BRENT_X
+// every instantiation by its template arguments: one list produces key and kernel, so a key cannot name another kernel
+typedef void (*BrentFn)(DevArgs, int);
+#define PM_BRENT_X(part, ...) {{__VA_ARGS__}, k_brent<__VA_ARGS__>},
+static const struct { pmplan::BrentKey key; BrentFn fn; } kBrentTable[] = {PM_BRENT_VARIANTS};
+#undef PM_BRENT_X
+static_assert(pmplan::kPdLo == PM_PD_LO && pmplan::kPdHi == PM_PD_HI && pmplan::kEpe == PM_EPE && pmplan::kDnPfC == DN_PF_C &&
+              pmplan::kDnPfBuf == DN_PF_BUF && pmplan::kQWave == QWAVE, "brent_plan.h restates engine_dev.h's constants");
 
 // ------------------------------------------------------------------------------------------------
 // error reporting (thread-local, C ABI)
@@ -22,6 +31,7 @@ struct pm_engine {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   pm_params par;
+  pmplan::EngineSwitches sw;   // the PM_* environment switches as pm_engine_create found them
   int n_fam = 0, n_person = 0, max_batch = 0;
   int chrom = PM_CHR_AUTO;
   int T = 64, S = 1;
@@ -94,9 +104,8 @@ struct pm_engine {
   int *d_ext_count1 = nullptr, *d_ext_fam1 = nullptr;
   // --quick_call: the MakeUnrelated() plan (every family an all-founder product) with its own geometry
   int Tq = 0, Sq = 0, grid_q = 0;
-  int quad_bpc16 = 0, quad_bpc8 = 0;   // QUAD k_brent blocks resident per CU (occupancy query, first launch)
   bool units_empty = false, units1_empty = false;   // a lane plan with no nuclear or founder unit (every family peeled)
-  std::vector<std::pair<const void*, int>> ep_bpc;   // EP one-wave k_brent blocks resident per CU, per instantiation
+  std::vector<std::pair<const void*, int>> bpc;   // QUAD / EP one-wave k_brent blocks resident per CU, per instantiation
   bool all_trio = false;   // every unit of the lane plan is a 3-person nuclear family (or empty): k_brent's NF = 3
   bool split34 = false;    // plan_split34: quads in the first half of the slot rows, trios in the second (NF = 34)
   int4* d_units_q = nullptr;
@@ -173,8 +182,17 @@ static int dalloc(X** p, size_t count) {
 static int xcd_grid(int g) { return g >= 8 ? g - g % 8 : std::max(g, 1); }
 #define DALLOC(p, n) do { int _r = dalloc(&(p), (n)); if (_r) { pm_engine_destroy(E); return _r; } } while (0)
 
-static const struct { int T, S; } kVariants[] = {{64, 1}, {64, 2}, {64, 4}, {128, 4}, {128, 16}, {256, 1}, {256, 4}, {512, 2}, {512, 4},
-                                                 {1024, 1}, {1024, 2}, {1024, 4}, {1024, 8}, {128, 8}, {64, 8}, {64, 16}};
+// What brent_plan.h's functions read from the engine (pm_engine_create calls it with the fields it has set so far).
+static pmplan::Facts facts_of(const pm_engine* E) {
+  pmplan::Facts f;
+  f.n_person = E->n_person; f.n_fam = E->n_fam; f.chrom = E->chrom; f.numerics = E->par.numerics; f.max_nuc = E->max_nuc;
+  f.denovo = E->par.denovo != 0; f.quick_call = E->par.quick_call != 0; f.vcf = E->vcf; f.use_plan1 = E->use_plan1;
+  f.has_fp = E->has_fp; f.es_poly = E->es_poly; f.quad = E->quad; f.all_trio = E->all_trio; f.split34 = E->split34;
+  f.plan[0] = {E->T, E->S, E->n_ext, E->units_empty, E->ep_dmax[0][E->chrom]};
+  f.plan[1] = {E->T1, E->S1, E->n_ext1, E->units1_empty, E->ep_dmax[1][E->chrom]};
+  f.quick = {E->Tq, E->Sq};
+  return f;
+}
 
 // Deal families to lanes: family-major round robin; founders-only families are split into <=3-person chunks
 // kept on one lane.  Returns false if the plan does not fit T x S.
@@ -374,7 +392,9 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
   E->vcf = par->vcf_mode != 0;
   if (E->vcf) { E->par.denovo = 0; E->par.quick_call = 0; }   // the VCF path has neither (PedVCF.cpp)
   par = &E->par;
-  if (const char* s = getenv("PM_TEST_ITMAX"); s && atoi(s) > 0) E->itmax = std::min(200, atoi(s));
+  E->sw = pmplan::EngineSwitches::from_env();   // every engine switch is read here, once
+  const pmplan::EngineSwitches& sw = E->sw;
+  if (sw.test_itmax > 0) E->itmax = std::min(200, sw.test_itmax);
   E->n_fam = ped->n_fam;
   E->n_person = ped->n_person;
   E->max_batch = max_batch;
@@ -459,52 +479,14 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
       if (stat + per_wave * w <= 150 * 1024) E->hoist_waves = w;
     if (!E->hoist_waves) E->es_poly = false;
   }
-  // plan
+  // plan 0: PM_BRENT_TS="T,S" (geometry experiments), else the first geometry in preference order that holds every family
   std::vector<int4> units;
-  bool planned = false;
-  // optional override for geometry experiments: PM_BRENT_TS="T,S"
-  if (const char* ov = getenv("PM_BRENT_TS")) {
-    int t = 0, sl = 0;
-    if (sscanf(ov, "%d,%d", &t, &sl) == 2)
-      for (auto v : kVariants)
-        if (v.T == t && v.S == sl && plan_units(ped, t, sl, units)) { E->T = t; E->S = sl; planned = true; }
-  }
-  // default: the first geometry (in preference order) that holds every family.  One wave per item
-  // (T=64, no barrier) wins while its slots fit the register file without scratch: up to S=16 for the
-  // lean autosomal kernel, S=8 for the generic one (de novo / founders-only units); beyond that the item
-  // is spread over 2-8 waves (one barrier per evaluation).  Sections on chrX/Y/MT run the generic
-  // kernel on the same plan.
-  {
-    const bool gen = (par->denovo && par->numerics != PM_NUM_POLY) || E->has_fp || ped->n_fam == 1;
-    // (1025-2048 families: 2 waves x 16 slots, one two-wave exchange per evaluation, before 8 waves x 4)
-    static const int2 lean[] = {{64, 1}, {64, 2}, {64, 4}, {64, 8}, {64, 16}, {128, 16}, {1024, 4}, {1024, 8}};
-    static const int2 generic[] = {{64, 1}, {64, 2}, {64, 4}, {64, 8}, {256, 1}, {256, 4}, {512, 4}, {1024, 4}, {1024, 8}};
-    // lean --denovo: the de novo hoisting state does not fit 16 slots per lane without spilling; 8 slots on
-    // 2 waves per item is faster (measured: 6.6 vs 6.1 M sites/s, 1000 quads)
-    static const int2 lean_dn[] = {{64, 1}, {64, 2}, {64, 4}, {64, 8}, {128, 8}, {512, 4}, {1024, 4}, {1024, 8}};
-    const bool dn_lean = !gen && par->denovo;
-    // ... unless the PL bytes can be staged through LDS (16-B aligned planes): then the 64 x 16 kernel with
-    // LDS-staged hoisting only has no spills and beats 2 waves x 8 slots (11.9 vs 9.8 M sites/s, 1000 quads)
-    static const int2 lean_dn_pf[] = {{64, 1}, {64, 2}, {64, 4}, {64, 8}, {64, 16}, {512, 4}, {1024, 4}, {1024, 8}};
-    const bool dn_pf = dn_lean && par->numerics == PM_NUM_POLY && E->max_nuc <= 4 && ped->n_person % 16 == 0 &&
-                       ped->n_person >= 16 && !getenv("PM_NO_PREFETCH");
-    const int2* pref = gen ? generic : dn_lean ? (dn_pf ? lean_dn_pf : lean_dn) : lean;
-    // extended families are the expensive terms: spread them one per lane up to 256 lanes
-    // (polynomial form: up to PM_EPE families per lane, their coefficients in registers, one wave per item)
-    // (--denovo too: the 10-state peels are hoisted by the schedule compiler's es_hoist_wave, and k_brent only
-    // evaluates their coefficients; the reference-order 10-state peel of PRODUCT / EXACT numerics keeps one per lane)
-    // (PM_EP_DN_ONE=1: one per lane under --denovo -- an experiment switch)
-    const int per_lane = (E->es_poly && !(par->denovo && getenv("PM_EP_DN_ONE"))) ? PM_EPE : 1;
-    int tmin = 1;
-    while (tmin < std::min((E->n_ext + per_lane - 1) / per_lane, 256)) tmin *= 2;
-    const int npref = gen ? 9 : 8;
-    for (int i = 0; i < npref && !planned; i++)
-      if (pref[i].x >= tmin && plan_units(ped, pref[i].x, pref[i].y, units)) { E->T = pref[i].x; E->S = pref[i].y; planned = true; }
-  }
-  if (!planned) { pm_engine_destroy(E); pm_set_last_error("pm_engine_create: pedigree too large for the lane plan"); return PM_EPED; }
+  const pmplan::Geometry g0 = pmplan::choose_geometry(facts_of(E), sw, [&](int t, int s) { return plan_units(ped, t, s, units); });
+  E->T = g0.T; E->S = g0.S;
+  if (!g0.T) { pm_engine_destroy(E); pm_set_last_error("pm_engine_create: pedigree too large for the lane plan"); return PM_EPED; }
   // mixed trio / quad pedigrees on the lean one- or two-wave 16-slot plans: the split layout (PM_NO_SPLIT34=1: off)
   if (!par->denovo && par->numerics == PM_NUM_POLY && !E->has_fp && E->n_ext == 0 && E->S == 16 && (E->T == 64 || E->T == 128) &&
-      !getenv("PM_NO_SPLIT34")) {
+      !sw.no_split34) {
     std::vector<int4> u2;
     if (plan_split34(ped, E->T, E->S, u2)) { units.swap(u2); E->split34 = true; }
   }
@@ -517,7 +499,7 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
         if (u.x == U_NONE) { full = std::min(full, sl); continue; }
         if (u.x != U_NUC || u.w != 4 || u.z != 4 * (sl * E->T + l)) { q = false; break; }
       }
-    E->quad = q && !getenv("PM_NO_QUAD");
+    E->quad = q && !sw.no_quad;
     E->quad_full = full;
   }
   hipDeviceProp_t prop;
@@ -654,10 +636,9 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
       }
       int tmin = 1;
       while (tmin < std::min(std::max(n1, 1), 256)) tmin *= 2;
-      static const int2 gp[] = {{64, 1}, {64, 2}, {64, 4}, {64, 8}, {256, 4}, {512, 4}, {1024, 4}, {1024, 8}};
       std::vector<int4> u1;
-      for (auto g : gp)
-        if (g.x >= tmin && plan_units(ped, g.x, g.y, u1, false, true)) { E->T1 = g.x; E->S1 = g.y; break; }
+      for (const pmplan::Geometry* g = pmplan::kPeeled; g->T && !E->T1; g++)
+        if (g->T >= tmin && plan_units(ped, g->T, g->S, u1, false, true)) { E->T1 = g->T; E->S1 = g->S; }
       if (!E->T1) E->plan1_ok = false;
       else {
         E->n_ext1 = n1;
@@ -697,7 +678,7 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
       const size_t per_item = (size_t)std::max({E->max_ext * E->T, E->max_ext1 * std::max(1, E->T1), 1}) * E->poly_dcap * sizeof(double);
       const size_t want = ((size_t)4 * std::max(1, max_batch) + 11) / 12 * 12;
       E->es_chunk = (int)std::max<size_t>(1, std::min<size_t>(want, ((size_t)1 << 32) / per_item));
-      if (const char* s = getenv("PM_ES_CHUNK"); s && atoi(s) > 0) E->es_chunk = std::min(E->es_chunk, atoi(s));
+      if (sw.es_chunk > 0) E->es_chunk = std::min(E->es_chunk, sw.es_chunk);
       if (E->es_chunk >= 12) E->es_chunk -= E->es_chunk % 12;   // whole sites of lists 0 and 1 per chunk (grouped tasks)
       // (a full-batch chunk that does not fit -- several engines per GPU, a smaller device -- falls back to the 1 GiB
       // chunk: launch_brent loops over chunks)
@@ -727,10 +708,9 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
   }
   // --- --quick_call: the unrelated plan (all persons in <=3-person founder chunks)
   if (par->quick_call) {
-    static const int2 gq[] = {{64, 1}, {64, 2}, {64, 4}, {64, 8}, {256, 4}, {512, 4}, {1024, 4}, {1024, 8}};
     std::vector<int4> uq;
-    for (auto g : gq)
-      if (plan_units(ped, g.x, g.y, uq, true)) { E->Tq = g.x; E->Sq = g.y; break; }
+    for (const pmplan::Geometry* g = pmplan::kPeeled; g->T && !E->Tq; g++)
+      if (plan_units(ped, g->T, g->S, uq, true)) { E->Tq = g->T; E->Sq = g->S; }
     if (!E->Tq) { pm_engine_destroy(E); pm_set_last_error("pm_engine_create: pedigree too large for the --quick_call lane plan"); return PM_EPED; }
     E->grid_q = E->n_cu * std::max(1, 1024 / E->Tq);
     DALLOC(E->d_units_q, uq.size());
@@ -757,7 +737,7 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
   DALLOC(E->d_counters, 16);
   HIP_TRY(hipMemset(E->d_counters, 0, 16 * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(E->d_eval_total, 0, sizeof(unsigned long long)));
-  if (getenv("PM_PHASE_TIMING")) {
+  if (sw.phase_timing) {
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) E->wall_khz = khz;
     DALLOC(E->d_phase, 3);
@@ -804,13 +784,6 @@ int pm_engine_begin_section(pm_engine* E, int32_t chrom) {
   HIP_TRY(hipMemsetAsync(E->d_counters, 0, 16 * sizeof(unsigned long long), E->stream));
   HIP_TRY(hipStreamSynchronize(E->stream));
   return PM_OK;
-}
-
-// lean autosomal --denovo (POLY numerics, nuclear families only, no quick pre-filter): k_prep evaluates
-// the cfg-0 de novo monomorphism item itself instead of enqueueing it for k_brent
-static bool mono_dn_in_prep(const pm_engine* E) {
-  return E->par.denovo && E->par.numerics == PM_NUM_POLY && !E->par.quick_call && !E->vcf && E->chrom == PM_CHR_AUTO &&
-         !E->has_fp && E->n_ext == 0 && E->n_fam > 1;
 }
 
 static DevArgs make_args(pm_engine* E, int n, const uint8_t* pl, const uint32_t* dm, const uint8_t* ref, pm_site_result* res,
@@ -860,81 +833,8 @@ static DevArgs make_args(pm_engine* E, int n, const uint8_t* pl, const uint32_t*
   A.carry_postprob = E->carry_postprob ? 1 : 0;
   A.itmax = E->itmax;
   A.qd_ctr = nullptr;
-  // (the QUAD plan's cfg-1 items form it from their hoisting: launch_brent takes the QUAD kernel for list 0 exactly when
-  // E->quad and the plan is 64 x 8 / 64 x 16, and mono_dn_in_prep already implies the lean --denovo kernel)
-  A.mono_dn = !mono_dn_in_prep(E) ? 0 : (E->quad && E->T == 64 && (E->S == 8 || E->S == 16) && !getenv("PM_MONO_DN_PREP")) ? 2 : 1;
+  A.mono_dn = pmplan::mono_dn(facts_of(E), E->sw);
   return A;
-}
-
-typedef void (*BrentFn)(DevArgs, int);
-// numerics: PM_NUM_PRODUCT / PM_NUM_EXACT for every flavour; PM_NUM_POLY only for the lean kernel
-// (the generic and ES flavours fall back to PRODUCT numerics).
-// pd_hi: the plan's peeled families reach a polynomial degree above PM_PD_LO (one-wave EP plans then take the
-// PM_PD_HI register tile; degrees above that are evaluated from the coefficient buffer)
-static BrentFn brent_kernel(int T, int S, int num, bool gen, bool es, bool dn = false, bool pf = false, bool ep = false, bool trio = false,
-                            bool epo = false, bool pd_hi = false, bool split34 = false) {
-  const int n = (num == PM_NUM_POLY && gen) ? PM_NUM_PRODUCT : num;
-  if (es && ep && epo && T == 64 && (S == 1 || S == 2 || S == 4)) {   // ep_only plans: the nuclear machinery compiled out
-#define PMKEO(s) \
-  if (S == s && pd_hi) return dn ? k_brent<64, s, PM_NUM_PRODUCT, true, true, true, false, true, false, 1, PM_PD_HI> \
-                                 : k_brent<64, s, PM_NUM_PRODUCT, true, true, false, false, true, false, 1, PM_PD_HI>; \
-  if (S == s) return dn ? k_brent<64, s, PM_NUM_PRODUCT, true, true, true, false, true, false, 1> \
-                        : k_brent<64, s, PM_NUM_PRODUCT, true, true, false, false, true, false, 1>;
-    PMKEO(1) PMKEO(2) PMKEO(4)
-#undef PMKEO
-  }
-  if (es && ep && pd_hi && T == 64) {
-#define PMKEH(s) \
-  if (S == s) return dn ? k_brent<64, s, PM_NUM_PRODUCT, true, true, true, false, true, false, 0, PM_PD_HI> \
-                        : k_brent<64, s, PM_NUM_PRODUCT, true, true, false, false, true, false, 0, PM_PD_HI>;
-    PMKEH(1) PMKEH(2) PMKEH(4) PMKEH(8)
-#undef PMKEH
-  }
-  if (es && ep) {   // extended families in polynomial form (PM_NUM_POLY); DN: with the 10-state (--denovo) hoisting
-#define PMKEP(t, s) \
-  if (T == t && S == s) return dn ? k_brent<t, s, PM_NUM_PRODUCT, true, true, true, false, true> : k_brent<t, s, PM_NUM_PRODUCT, true, true, false, false, true>;
-    PMKEP(64, 1) PMKEP(64, 2) PMKEP(64, 4) PMKEP(64, 8) PMKEP(256, 1) PMKEP(256, 4) PMKEP(512, 4) PMKEP(1024, 4) PMKEP(1024, 8)
-#undef PMKEP
-    return nullptr;
-  }
-  if (dn && !gen && !es && n == PM_NUM_POLY && pf && T == 64 && S == 16)   // lean --denovo, LDS-staged hoisting only
-    return k_brent<64, 16, PM_NUM_POLY, false, false, true, true>;
-  if (pf && !dn && split34 && S == 16) {   // mixed trio / quad split plans
-    if (T == 64) return k_brent<64, 16, PM_NUM_POLY, false, false, false, true, false, false, 34>;
-    if (T == 128) return k_brent<128, 16, PM_NUM_POLY, false, false, false, true, false, false, 34>;
-  }
-  if (pf && !dn) {   // lean autosomal kernel with LDS plane prefetch
-#define PMKP(s) if (T == 64 && S == s) return trio ? k_brent<64, s, PM_NUM_POLY, false, false, false, true, false, false, 3> \
-                                                   : k_brent<64, s, PM_NUM_POLY, false, false, false, true>;
-    PMKP(1) PMKP(2) PMKP(4) PMKP(8) PMKP(16)
-#undef PMKP
-    if (T == 128 && S == 16)   // 1025-2048 families
-      return trio ? k_brent<128, 16, PM_NUM_POLY, false, false, false, true, false, false, 3> : k_brent<128, 16, PM_NUM_POLY, false, false, false, true>;
-    return nullptr;
-  }
-  if (dn && !gen && !es && n == PM_NUM_POLY) {   // lean autosomal --denovo
-#define PMKD(t, s) if (T == t && S == s) return k_brent<t, s, PM_NUM_POLY, false, false, true>;
-    PMKD(64, 1) PMKD(64, 2) PMKD(64, 4) PMKD(64, 8) PMKD(64, 16) PMKD(128, 8) PMKD(512, 4) PMKD(1024, 4) PMKD(1024, 8)
-#undef PMKD
-    return nullptr;
-  }
-#define PMK(t, s)                                                                                             \
-  if (T == t && S == s) {                                                                                     \
-    if (gen) return n == PM_NUM_EXACT ? k_brent<t, s, PM_NUM_EXACT, true, false> : k_brent<t, s, PM_NUM_PRODUCT, true, false>; \
-    return n == PM_NUM_EXACT ? k_brent<t, s, PM_NUM_EXACT, false, false>                                      \
-         : n == PM_NUM_POLY ? k_brent<t, s, PM_NUM_POLY, false, false> : k_brent<t, s, PM_NUM_PRODUCT, false, false>; \
-  }
-#define PMKE(t, s) \
-  if (T == t && S == s) return n == PM_NUM_EXACT ? k_brent<t, s, PM_NUM_EXACT, true, true> : k_brent<t, s, PM_NUM_PRODUCT, true, true>;
-  if (es) {
-    PMKE(64, 1) PMKE(64, 2) PMKE(64, 4) PMKE(64, 8) PMKE(256, 1) PMKE(256, 4) PMKE(512, 4) PMKE(1024, 4) PMKE(1024, 8)
-    return nullptr;
-  }
-  PMK(64, 1) PMK(64, 2) PMK(64, 4) PMK(128, 4) PMK(256, 4) PMK(512, 2) PMK(512, 4) PMK(1024, 1) PMK(1024, 2)
-  PMK(1024, 4) PMK(1024, 8) PMK(128, 8) PMK(64, 8) PMK(64, 16) PMK(128, 16)
-#undef PMK
-#undef PMKE
-  return nullptr;
 }
 
 // The extended families of the current plan as the schedule compiler sees them (slot order e = q * T + lane).
@@ -961,7 +861,7 @@ static std::vector<pmjit::Family> jit_families(const pm_engine* E, int plan) {
 // when it is off (PM_NO_JIT) or failed to build (then the generic k_es_hoist / k_posterior_es run).
 static const pmjit::Kernel* jit_kernel(pm_engine* E) {
   const int plan = E->use_plan1 ? 1 : 0, cls = E->chrom;
-  if (!E->es_poly || getenv("PM_NO_JIT")) return nullptr;
+  if (!E->es_poly || E->sw.no_jit) return nullptr;
   int& st = E->jit_state[plan][cls];
   if (st == 0) {
     st = -1;
@@ -969,7 +869,7 @@ static const pmjit::Kernel* jit_kernel(pm_engine* E) {
     std::string err;
     pmjit::Kernel& K = E->jit[plan][cls];
     // (--denovo outside vcf_mode: every de novo item is hoisted in a grouped task, launch_brent)
-    const int dmode = !E->par.denovo ? 0 : (!E->vcf && !getenv("PM_ES_NOGROUP")) ? 2 : 1;
+    const int dmode = !E->par.denovo ? 0 : (!E->vcf && !E->sw.es_nogroup) ? 2 : 1;
     if (!fams.empty() && pmjit::build(E->device, cls, fams, kTBA, dmode, &K, &err)) {
       const size_t ns = K.slot_e.size();
       std::vector<int> tab(3 * ns + K.pair_k.size());   // slot_e | slot_sig | slot_p0 | pair_k (es_hoist_wave)
@@ -988,7 +888,7 @@ static const pmjit::Kernel* jit_kernel(pm_engine* E) {
 // first use; nullptr when off (PM_NO_FUSED, PM_NO_JIT) or unavailable (then es_hoist_jit + k_brent run).
 static const pmjit::FusedKernel* fused_kernel(pm_engine* E) {
   const int plan = E->use_plan1 ? 1 : 0, cls = E->chrom;
-  if (!E->es_poly || getenv("PM_NO_JIT") || getenv("PM_NO_FUSED")) return nullptr;
+  if (!E->es_poly || E->sw.no_jit || E->sw.no_fused) return nullptr;
   int& st = E->fused_state[plan][cls];
   if (st == 0) {
     st = -1;
@@ -999,98 +899,153 @@ static const pmjit::FusedKernel* fused_kernel(pm_engine* E) {
       if (dalloc(&E->d_fused_tab[plan][cls], F.lane_tab.size()) == PM_OK &&
           hipMemcpy(E->d_fused_tab[plan][cls], F.lane_tab.data(), sizeof(int) * F.lane_tab.size(), hipMemcpyHostToDevice) == hipSuccess)
         st = 1;
-    } else if (!fams.empty() && getenv("PM_JIT_LAYOUT"))
+    } else if (!fams.empty() && E->sw.jit_layout)
       fprintf(stderr, "polymutt: fused Brent kernel unavailable (%s); hoisting + k_brent\n", err.c_str());
   }
   return st == 1 ? &E->fused[plan][cls] : nullptr;
 }
 
+// HIP events around a launch (pm_kernel_stats reports Brent and EP hoisting launches apart): begin pushes a fresh pair
+// and records its first event, end records the last pair's second
+static int mark(pm_engine* E, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, bool begin) {
+  if (begin) {
+    v.push_back({nullptr, nullptr});
+    HIP_TRY(hipEventCreate(&v.back().first));
+    HIP_TRY(hipEventCreate(&v.back().second));
+  }
+  HIP_TRY(hipEventRecord(begin ? v.back().first : v.back().second, E->stream));
+  return PM_OK;
+}
+
+// Blocks of a one-wave k_brent instantiation resident per CU (occupancy query on first use).
+static int resident_blocks(pm_engine* E, BrentFn fn, int T, size_t lds) {
+  for (auto& c : E->bpc)
+    if (c.first == (const void*)fn) return c.second;
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, T, lds) != hipSuccess || n <= 0) {
+    (void)hipGetLastError();
+    n = 1024 / T;
+  }
+  E->bpc.push_back({(const void*)fn, n});
+  return n;
+}
+
+// One k_brent launch between its pair of events.
+static int launch_plain(pm_engine* E, BrentFn fn, int grid, int T, size_t lds, const DevArgs& A, int list) {
+  if (int rc = mark(E, E->brent_events, true)) return rc;
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(T), lds, E->stream, A, list);
+  HIP_TRY(hipGetLastError());
+  return mark(E, E->brent_events, false);
+}
+
+// Bi-allelic engines whose every family is peeled (config 4): one fused launch per list -- each lane hoists its
+// families' polynomials into registers and the wave runs the item's Brent (es_jit.h ep_brent_jit)
+static int launch_fused(pm_engine* E, const pmjit::FusedKernel* FK, const DevArgs& A, int list) {
+  E->es_ops_known = true;   // (finish_batch: every item is bi-allelic, o[0] = one item's hoisting over every family)
+  for (int v = 0; v < 6; v++) E->es_item_ops[v] = v == 0 ? FK->item_ops : 0.0;
+  pmjit::FusedArgs F;
+  F.items = A.items[list]; F.counts = A.counts; F.ref = A.ref; F.res = (const int*)A.res; F.pl = A.pl; F.lktab = A.lktab;
+  F.lane_tab = E->d_fused_tab[E->use_plan1 ? 1 : 0][E->chrom];
+  F.raw = A.raw; F.minv = A.minv; F.evals = A.evals; F.eval_total = A.eval_total; F.precision = A.precision;
+  F.list = list; F.it0 = 0; F.it1 = INT_MAX; F.np = A.n_person; F.vcf = A.vcf; F.res_words = sizeof(pm_site_result) / 4;
+  F.res_a1 = offsetof(pm_site_result, allele1) / 4; F.res_a2 = offsetof(pm_site_result, allele2) / 4;
+  F.itmax = A.itmax; F.pad = 0;
+  void* params[] = {&F};
+  if (int rc = mark(E, E->brent_events, true)) return rc;
+  // (PM_FUSED_ROUNDS rounds of the resident blocks: measured)
+  HIP_TRY(hipModuleLaunchKernel(FK->fn, xcd_grid(E->n_cu * FK->blocks_per_cu * E->sw.fused_rounds), 1, 1, 64, 1, 1, 0, E->stream, params,
+                                nullptr));
+  return mark(E, E->brent_events, false);
+}
+
+// Extended families in polynomial form, in chunks of the list (the coefficient buffer holds es_chunk items): the hoisting
+// (the schedule compiler's kernel, else k_es_hoist), then the chunk's Brent items
+static int launch_ep_chunks(pm_engine* E, BrentFn fn, int grid, int T, size_t lds, DevArgs A, int list) {
+  void (*hoist)(DevArgs, int) = A.denovo ? k_es_hoist<true> : k_es_hoist<false>;
+  const size_t hlds = (size_t)E->hoist_waves * (E->poly_coef + E->hoist_tmp) * sizeof(double);
+  if (hlds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)hoist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hlds));
+  const size_t stat = (256 + 5 * 27 + (A.denovo ? 2000 : 2)) * sizeof(double);
+  const int hgrid = E->n_cu * std::max(1, std::min(8, (int)((160 * 1024) / (hlds + stat))));
+  const int max_items = 4 * E->last_n;
+  const pmjit::Kernel* K = jit_kernel(E);
+  E->es_ops_known = K != nullptr;
+  for (int v = 0; v < 6 && K; v++) {   // one item's hoisting ops over the plan's extended families (slot shapes), by variant
+    E->es_item_ops[v] = 0;
+    for (int sg : K->slot_sig) E->es_item_ops[v] += K->shape_ops[v].empty() ? 0.0 : K->shape_ops[v][sg];
+  }
+  for (int it0 = 0; it0 < max_items; it0 += E->es_chunk) {
+    A.es_it0 = it0;
+    A.es_it1 = (int)std::min<long long>((long long)it0 + E->es_chunk, INT_MAX);
+    if (int rc = mark(E, E->es_events, true)) return rc;
+    if (K) {   // compiled schedule: one thread (--denovo: one wave) per (item, family)
+      const int plan = E->use_plan1 ? 1 : 0, ns = (int)K->slot_e.size();
+      const int* tab = E->d_jit_slots[plan][E->chrom];
+      pmjit::Args J;
+      J.items = A.items[list]; J.counts = A.counts; J.ref = A.ref; J.res = (const int*)A.res; J.pl = A.pl; J.lktab = A.lktab;
+      J.coef = A.es_coef; J.slot_e = tab; J.slot_sig = tab + ns; J.slot_p0 = tab + 2 * ns;
+      J.pair_k = tab + 3 * ns; J.npairs = (int)K->pair_k.size() / 2;
+      J.T10 = E->d_T10; J.T10dn = E->d_T10dn; J.tba = E->d_tba;
+      J.list = list; J.it0 = A.es_it0; J.it1 = A.es_it1; J.nslots = ns; J.np = A.n_person; J.T = A.T; J.max_ext = A.max_ext;
+      J.dcap = A.poly_dcap; J.vcf = A.vcf; J.res_words = sizeof(pm_site_result) / 4;
+      J.res_a1 = offsetof(pm_site_result, allele1) / 4; J.res_a2 = offsetof(pm_site_result, allele2) / 4;
+      J.denovo = A.denovo;
+      J.prof = nullptr;
+      if (E->sw.es_prof) {
+        if (!E->d_es_prof) {
+          if (int r = dalloc(&E->d_es_prof, 5)) return r;
+          HIP_TRY(hipMemset(E->d_es_prof, 0, 5 * sizeof(unsigned long long)));
+        }
+        J.prof = E->d_es_prof;
+      }
+      // a site's de novo items are consecutive in lists 0 (cfgs 0-3, or 1-3 when k_prep / the QUAD item takes the
+      // monomorphism) and 1 (cfgs 4-6): one task takes them together, the 10-state leaf steps once
+      J.group = 0;
+      if (K->wave && A.denovo && !A.vcf && !E->sw.es_nogroup) {
+        if (list == 0) J.group = A.mono_dn ? 3 : 4;
+        else if (list == 1) J.group = 3;
+      }
+      if (list == 0) E->es_grouped = J.group > 1;   // (finish_batch's op count: lists 0 and 1 group alike)
+      void* params[] = {&J};
+      if (K->wave)
+        HIP_TRY(hipModuleLaunchKernel(K->fn, E->n_cu * (K->blocks_per_cu > 0 ? K->blocks_per_cu : std::max(1, 16 / K->wpb)), 1, 1,
+                                      64 * K->wpb, 1, 1, 0, E->stream, params, nullptr));
+      else
+        HIP_TRY(hipModuleLaunchKernel(K->fn, E->n_cu * 8, 1, 1, 256, 1, 1, 0, E->stream, params, nullptr));
+    } else hipLaunchKernelGGL(hoist, dim3(hgrid), dim3(64 * E->hoist_waves), hlds, E->stream, A, list);
+    HIP_TRY(hipGetLastError());
+    if (int rc = mark(E, E->es_events, false)) return rc;
+    if (int rc = launch_plain(E, fn, grid, T, lds, A, list)) return rc;
+  }
+  return PM_OK;
+}
+
+// One list's Brent items: select the kernel (brent_plan.h), resolve it, adjust launch to the device, launch.
 static int launch_brent(pm_engine* E, const DevArgs& A0, int list, bool unrelated = false) {
   DevArgs A = A0;
-  int T = E->T, S = E->S, grid = E->grid_brent;
-  // lean kernel: autosome, no de novo model, nuclear families only (the common case)
-  // (with POLY numerics the lean kernel also takes autosomal --denovo: its hoisting has the de novo kid terms)
-  bool gen = E->chrom != PM_CHR_AUTO || (E->par.denovo && E->par.numerics != PM_NUM_POLY) || E->has_fp || E->n_fam == 1;
-  int n_ext = E->n_ext;
-  if (E->use_plan1) { T = E->T1; S = E->S1; grid = E->grid1; gen = true; n_ext = E->n_ext1; }
-  if (unrelated) {   // MakeUnrelated(): all-founder products over the quick plan, no ES, no de novo model
-    A.units = E->d_units_q; A.T = T = E->Tq; A.S = S = E->Sq; grid = E->grid_q;
-    A.ext_count = nullptr; A.unrelated = 1; A.denovo = 0; gen = true;
-  } else A.unrelated = 0;
-  // lean non-de-novo kernel at one wave per item: LDS-DMA plane prefetch when the planes are 16-B aligned
-  size_t shmem = 0;
-  A.pf_npad = 0;
-  A.pf_dw = 0;
-  // (16-B pieces need 16-B aligned planes: n_person % 16 == 0 and a 16-B aligned block; 4-B pieces otherwise; the
-  // 128 x 16 plan of 1025-2048 families shares one buffer between its two waves)
-  const bool al16 = E->n_person % 16 == 0 && ((uintptr_t)A.pl & 15) == 0, al4 = E->n_person % 4 == 0 && ((uintptr_t)A.pl & 3) == 0;
-  if (!gen && !unrelated && n_ext == 0 && !A.denovo && (T == 64 || (T == 128 && S == 16)) && E->par.numerics == PM_NUM_POLY &&
-      E->max_nuc <= 4 && (al16 || al4) && E->n_person >= 16 && (E->n_person + 1023) / 1024 * 1024 * 3 <= 60 * 1024 &&
-      !getenv("PM_NO_PREFETCH")) {
-    A.pf_npad = (E->n_person + 1023) / 1024 * 1024;
-    A.pf_stride = A.pf_npad + 16;
-    A.pf_dw = al16 ? 0 : 1;
-    shmem = (size_t)3 * A.pf_stride;
-  }
-  // lean --denovo kernel: QUAD plans load each family's PL dwords directly (hoist_quad); other plans stage the PL
-  // windows through LDS by LDS-DMA (double buffer per wave)
-  A.dn_pf = 0;
-  A.quad_full = E->quad_full;
-  const bool quad = !gen && !unrelated && n_ext == 0 && A.denovo && E->par.numerics == PM_NUM_POLY && E->quad && T == 64 &&
-                    (S == 8 || S == 16);
-  if (quad) shmem = QWAVE;
-  // QUAD: list 0 holds cfgs 1-3 of each called site and list 1 cfgs 4-6, consecutive and site-aligned (k_prep / k_select
-  // reserve them three at a time): one wave takes a site's three in turn (PM_QD_GROUP=1: one item per step of the grid)
-  A.qd_group = 1;
-  if (quad && A.mono_dn == 2 && (list == 0 || list == 1)) {
-    const char* eg = getenv("PM_QD_GROUP");
-    A.qd_group = eg ? std::max(1, atoi(eg)) : 1;
-    if (A.qd_group != 1 && A.qd_group != 3) A.qd_group = 3;
-  }
-  BrentFn qfn = nullptr;
-  if (quad) {   // persistent grid = the blocks that are resident at once (PM_QD_WAVES per SIMD): no partial second round
-    qfn = S == 16 ? k_brent<64, 16, PM_NUM_POLY, false, false, true, false, false, true>
-                  : k_brent<64, 8, PM_NUM_POLY, false, false, true, false, false, true>;
-    int& bpc = S == 16 ? E->quad_bpc16 : E->quad_bpc8;
-    if (bpc == 0) {
-      int n = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)qfn, 64, shmem) != hipSuccess || n <= 0) {
-        (void)hipGetLastError();
-        n = 1024 / 64;
-      }
-      bpc = n;
-      if (getenv("PM_QD_BPC")) bpc = std::max(1, atoi(getenv("PM_QD_BPC")));
-    }
-    // PM_QD_ROUNDS = R rounds of the resident blocks (default 1): a block then takes 1 / R of the items it takes in a
-    // persistent grid, so the three items of a site -- started together on neighbouring blocks of one XCD -- drift
-    // apart by fewer items and find the site's planes still in that XCD's L2: FETCH per dispatch 4.81 GB at R = 1, 4.24
-    // at 2, 4.00 at 4, 3.96 at 8 (3.85 algorithmic), k_brent 3.19 -> 2.98 ms on one engine (profiles/r06l_*); but the
-    // default three engines then interleave their launches' blocks on every XCD and the bench's wall rate drops 1.5%
-    // (r06n_*), so R = 1 stays.  PM_QD_DYN=1: the per-XCD claimed item order (k_brent qd_ctr; slower, r06o_*).
-    const char* ed = getenv("PM_QD_DYN");
-    const bool dyn = ed && atoi(ed) != 0 && A.qd_group == 1;
-    if (dyn) {
+  const pmplan::EngineSwitches& sw = E->sw;
+  const int align = ((uintptr_t)A.pl & 15) == 0 ? 16 : ((uintptr_t)A.pl & 3) == 0 ? 4 : 1;
+  const pmplan::BrentChoice c = pmplan::brent_select(facts_of(E), sw, list, unrelated, align);
+  const int T = c.key.T, S = c.key.S;
+  int grid = unrelated ? E->grid_q : E->use_plan1 ? E->grid1 : E->grid_brent;
+  size_t shmem = c.lds;
+  if (unrelated) { A.units = E->d_units_q; A.T = T; A.S = S; A.ext_count = nullptr; A.denovo = 0; }
+  A.unrelated = unrelated ? 1 : 0;
+  A.pf_npad = c.pf_npad; A.pf_stride = c.pf_stride; A.pf_dw = c.pf_dw; A.dn_pf = c.dn_pf; A.qd_group = c.qd_group; A.quad_full = E->quad_full;
+  BrentFn fn = nullptr;
+  for (const auto& v : kBrentTable)
+    if (v.key == c.key) fn = v.fn;
+  if (!fn) { pm_set_last_error("launch_brent: no kernel variant for the lane plan"); return PM_EINVAL; }
+  if (c.quad) {   // persistent grid = the blocks that are resident at once (PM_QD_WAVES per SIMD): no partial second round
+    const int bpc = sw.qd_bpc ? sw.qd_bpc : resident_blocks(E, fn, 64, shmem);
+    // PM_QD_ROUNDS = R rounds of them keep a site's three items closer in one XCD's L2 (less traffic, a faster launch)
+    // but cost the three-engine wall rate 1.5%, so R = 1; PM_QD_DYN=1, the per-XCD claimed item order (k_brent qd_ctr),
+    // is slower ("Headline traffic explained": profiles/r06l_*, r06n_*, r06o_*)
+    if (sw.qd_dyn && A.qd_group == 1) {
       HIP_TRY(hipMemsetAsync(E->d_qctr, 0, 8 * sizeof(int), E->stream));
       A.qd_ctr = E->d_qctr;
     }
-    const char* er = getenv("PM_QD_ROUNDS");
-    const int rounds = getenv("PM_QD_BPC") ? 1 : er ? std::max(1, atoi(er)) : 1;
-    grid = E->n_cu * bpc * rounds;
-    grid = xcd_grid(grid);   // (the XCD-aware item order)
+    grid = xcd_grid(E->n_cu * bpc * (sw.qd_bpc ? 1 : sw.qd_rounds));   // (the XCD-aware item order)
   }
-  if (!quad && !gen && !unrelated && n_ext == 0 && A.denovo && E->par.numerics == PM_NUM_POLY && E->max_nuc <= 4 && S % DN_PF_C == 0 &&
-      E->n_person % 16 == 0 && E->n_person >= 16 && !getenv("PM_NO_PREFETCH")) {
-    A.dn_pf = 1;
-    shmem = (size_t)(T / 64) * 2 * DN_PF_BUF;
-  }
-  const bool ep = !unrelated && n_ext > 0 && E->es_poly && E->par.numerics == PM_NUM_POLY;
-  const bool ep_only = ep && (E->use_plan1 ? E->units1_empty : E->units_empty) && !getenv("PM_NO_EP_ONLY");
-  BrentFn fn = quad ? qfn
-                   : brent_kernel(T, S, E->par.numerics, gen, !unrelated && n_ext > 0, A.denovo != 0, A.pf_npad > 0 || A.dn_pf, ep,
-                                  E->all_trio && !unrelated && !getenv("PM_NO_TRIO"), ep_only && !getenv("PM_NO_EPO"),
-                                  ep && E->ep_dmax[E->use_plan1 ? 1 : 0][E->chrom] > PM_PD_LO && !getenv("PM_NO_PD_HI"),
-                                  E->split34 && !gen && !unrelated && !E->use_plan1);
-  if (!fn) { pm_set_last_error("launch_brent: no kernel variant for the lane plan"); return PM_EINVAL; }
   // multi-wave de novo plans (T = 512 / 1024: more than 1024 families) stage 2 buffers per wave: above the
   // default 64 KB dynamic-LDS limit the kernel must opt in, and the block (plus its static LDS: lane plan,
   // tables) must fit one CU's 160 KB; otherwise the same kernel hoists from direct loads
@@ -1104,10 +1059,10 @@ static int launch_brent(pm_engine* E, const DevArgs& A0, int list, bool unrelate
   // Elston-Stewart workspace in LDS: every partial / marriage-partial access of the peel becomes an LDS round
   // trip instead of an L2 one.  Blocks per CU follow from the LDS budget (160 KB per CU).
   A.ws_lds = 0;
-  if (ep) {   // polynomial-form peels: coefficients from k_es_hoist, no workspace in k_brent
+  if (c.ep) {   // polynomial-form peels: coefficients from k_es_hoist, no workspace in k_brent
     A.es_poly = 1;
-    A.ep_only = ep_only;
-  } else if (!unrelated && n_ext > 0 && !E->par.denovo) {   // BA peels (the 10-state one is too big)
+    A.ep_only = c.ep_only;
+  } else if (c.key.ES && !E->par.denovo) {   // BA peels (the 10-state one is too big)
     const size_t need = (size_t)E->ws_per_lane * T * sizeof(double);
     if (need > 0 && need <= 150 * 1024) {
       if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need) == hipSuccess) {
@@ -1117,133 +1072,16 @@ static int launch_brent(pm_engine* E, const DevArgs& A0, int list, bool unrelate
       } else (void)hipGetLastError();
     }
   }
-  if (ep && T == 64) {   // EP one-wave plans: a persistent grid of exactly the resident blocks (no partial second round)
-    int bpc = 0;
-    for (auto& c : E->ep_bpc)
-      if (c.first == (const void*)fn) bpc = c.second;
-    if (bpc == 0) {
-      int n = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, T, shmem) != hipSuccess || n <= 0) {
-        (void)hipGetLastError();
-        n = 1024 / T;
-      }
-      bpc = n;
-      E->ep_bpc.push_back({(const void*)fn, n});
-    }
-    grid = std::min(grid, E->n_cu * bpc);
-    grid = xcd_grid(grid);
-  }
-  // lean PF kernels: PM_PF_ROUNDS x the default grid (2 rounds of the resident blocks).  One-wave quad plans take 4 (8
-  // rounds): less drift between the items of a site, so its planes are re-read from L2 (plain quads 27.7 -> 28.7 M
-  // sites/s, k_brent frac 0.725 -> 0.76, profiles/r06m_*).  Trio plans lost 2% of wall rate with it (frac 0.70 -> 0.72:
-  // the engines' launches interleave, r06p_*) and the two-wave 128 x 16 plans (config 5) gained nothing: 1
-  if (A.pf_npad > 0 && !ep) {
-    const char* epr = getenv("PM_PF_ROUNDS");
-    const int r = epr ? std::max(1, atoi(epr)) : (T == 64 && !E->all_trio) ? 4 : 1;
-    grid = xcd_grid(grid * r);
-  }
-  // HIP events around every Brent launch (and, for EP, every hoisting launch: pm_kernel_stats reports the two apart)
-  auto mark = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, bool begin) -> int {
-    if (begin) {
-      hipEvent_t a, b;
-      HIP_TRY(hipEventCreate(&a));
-      HIP_TRY(hipEventCreate(&b));
-      v.push_back({a, b});
-      HIP_TRY(hipEventRecord(a, E->stream));
-    } else HIP_TRY(hipEventRecord(v.back().second, E->stream));
-    return PM_OK;
-  };
-  int mrc;
-  // bi-allelic engines whose every family is peeled (config 4): one fused launch per list -- each lane hoists its
-  // families' polynomials into registers and the wave runs the item's Brent (es_jit.h ep_brent_jit)
-  const pmjit::FusedKernel* FK = (ep && ep_only && !A.denovo && T == 64) ? fused_kernel(E) : nullptr;
-  if (FK) {
-    E->es_ops_known = true;   // (finish_batch: every item is bi-allelic, o[0] = one item's hoisting over every family)
-    for (int v = 0; v < 6; v++) E->es_item_ops[v] = v == 0 ? FK->item_ops : 0.0;
-    const int plan = E->use_plan1 ? 1 : 0;
-    pmjit::FusedArgs F;
-    F.items = A.items[list]; F.counts = A.counts; F.ref = A.ref; F.res = (const int*)A.res; F.pl = A.pl; F.lktab = A.lktab;
-    F.lane_tab = E->d_fused_tab[plan][E->chrom];
-    F.raw = A.raw; F.minv = A.minv; F.evals = A.evals; F.eval_total = A.eval_total;
-    F.precision = A.precision;
-    F.list = list; F.it0 = 0; F.it1 = INT_MAX; F.np = A.n_person; F.vcf = A.vcf; F.res_words = sizeof(pm_site_result) / 4;
-    F.res_a1 = offsetof(pm_site_result, allele1) / 4; F.res_a2 = offsetof(pm_site_result, allele2) / 4;
-    F.itmax = A.itmax; F.pad = 0;
-    void* params[] = {&F};
-    if ((mrc = mark(E->brent_events, true))) return mrc;
-    const char* efr = getenv("PM_FUSED_ROUNDS");   // (rounds of the resident blocks: measured)
-    const int frounds = efr ? std::max(1, atoi(efr)) : 1;
-    HIP_TRY(hipModuleLaunchKernel(FK->fn, xcd_grid(E->n_cu * FK->blocks_per_cu * frounds), 1, 1, 64, 1, 1, 0, E->stream, params,
-                                  nullptr));
-    if ((mrc = mark(E->brent_events, false))) return mrc;
-  } else if (ep) {   // chunks of the list (the coefficient buffer holds es_chunk items): k_es_hoist, then the chunk's Brent items
-    void (*hoist)(DevArgs, int) = A.denovo ? k_es_hoist<true> : k_es_hoist<false>;
-    const size_t hlds = (size_t)E->hoist_waves * (E->poly_coef + E->hoist_tmp) * sizeof(double);
-    if (hlds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)hoist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hlds));
-    const size_t stat = (256 + 5 * 27 + (A.denovo ? 2000 : 2)) * sizeof(double);
-    const int hgrid = E->n_cu * std::max(1, std::min(8, (int)((160 * 1024) / (hlds + stat))));
-    const int max_items = 4 * E->last_n;
-    const pmjit::Kernel* K = jit_kernel(E);
-    E->es_ops_known = K != nullptr;
-    if (K) {   // one item's hoisting ops over the plan's extended families (slot shapes), by variant
-      for (int v = 0; v < 6; v++) {
-        E->es_item_ops[v] = 0;
-        for (int sg : K->slot_sig) E->es_item_ops[v] += K->shape_ops[v].empty() ? 0.0 : K->shape_ops[v][sg];
-      }
-    }
-    for (int it0 = 0; it0 < max_items; it0 += E->es_chunk) {
-      A.es_it0 = it0;
-      A.es_it1 = (int)std::min<long long>((long long)it0 + E->es_chunk, INT_MAX);
-      if ((mrc = mark(E->es_events, true))) return mrc;
-      if (K) {   // compiled schedule: one thread (--denovo: one wave) per (item, family)
-        const int plan = E->use_plan1 ? 1 : 0, ns = (int)K->slot_e.size();
-        const int* tab = E->d_jit_slots[plan][E->chrom];
-        pmjit::Args J;
-        J.items = A.items[list]; J.counts = A.counts; J.ref = A.ref; J.res = (const int*)A.res; J.pl = A.pl; J.lktab = A.lktab;
-        J.coef = A.es_coef; J.slot_e = tab; J.slot_sig = tab + ns; J.slot_p0 = tab + 2 * ns;
-        J.pair_k = tab + 3 * ns; J.npairs = (int)K->pair_k.size() / 2;
-        J.T10 = E->d_T10; J.T10dn = E->d_T10dn; J.tba = E->d_tba;
-        J.list = list; J.it0 = A.es_it0; J.it1 = A.es_it1; J.nslots = ns; J.np = A.n_person; J.T = A.T; J.max_ext = A.max_ext;
-        J.dcap = A.poly_dcap; J.vcf = A.vcf; J.res_words = sizeof(pm_site_result) / 4;
-        J.res_a1 = offsetof(pm_site_result, allele1) / 4; J.res_a2 = offsetof(pm_site_result, allele2) / 4;
-        J.denovo = A.denovo;
-        // a site's de novo items are consecutive in lists 0 (cfgs 0-3, or 1-3 when k_prep / the QUAD item takes the
-        // monomorphism) and 1 (cfgs 4-6): one task takes them together, the 10-state leaf steps once
-        J.prof = nullptr;
-        if (getenv("PM_ES_PROF")) {
-          if (!E->d_es_prof) {
-            if (int r = dalloc(&E->d_es_prof, 5)) return r;
-            HIP_TRY(hipMemset(E->d_es_prof, 0, 5 * sizeof(unsigned long long)));
-          }
-          J.prof = E->d_es_prof;
-        }
-        J.group = 0;
-        if (K->wave && A.denovo && !A.vcf && !getenv("PM_ES_NOGROUP")) {
-          if (list == 0) J.group = A.mono_dn ? 3 : 4;
-          else if (list == 1) J.group = 3;
-        }
-        if (list == 0) E->es_grouped = J.group > 1;   // (finish_batch's op count: lists 0 and 1 group alike)
-        void* params[] = {&J};
-        if (K->wave)
-          HIP_TRY(hipModuleLaunchKernel(K->fn, E->n_cu * (K->blocks_per_cu > 0 ? K->blocks_per_cu : std::max(1, 16 / K->wpb)), 1, 1,
-                                        64 * K->wpb, 1, 1, 0, E->stream, params, nullptr));
-        else
-          HIP_TRY(hipModuleLaunchKernel(K->fn, E->n_cu * 8, 1, 1, 256, 1, 1, 0, E->stream, params, nullptr));
-      } else hipLaunchKernelGGL(hoist, dim3(hgrid), dim3(64 * E->hoist_waves), hlds, E->stream, A, list);
-      HIP_TRY(hipGetLastError());
-      if ((mrc = mark(E->es_events, false))) return mrc;
-      if ((mrc = mark(E->brent_events, true))) return mrc;
-      hipLaunchKernelGGL(fn, dim3(grid), dim3(T), shmem, E->stream, A, list);
-      HIP_TRY(hipGetLastError());
-      if ((mrc = mark(E->brent_events, false))) return mrc;
-    }
-  } else {
-    if ((mrc = mark(E->brent_events, true))) return mrc;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(T), shmem, E->stream, A, list);
-    HIP_TRY(hipGetLastError());
-    if ((mrc = mark(E->brent_events, false))) return mrc;
-  }
-  return PM_OK;
+  // EP one-wave plans: a persistent grid of exactly the resident blocks (no partial second round)
+  if (c.ep && T == 64) grid = xcd_grid(std::min(grid, E->n_cu * resident_blocks(E, fn, T, shmem)));
+  // lean PF kernels: PM_PF_ROUNDS x the default grid (2 rounds of the resident blocks).  One-wave quad plans take 4:
+  // their planes are re-read from L2 (+1.5-3.7%, profiles/r06m_*); trio plans lost 2% with it (r06p_*) and the two-wave
+  // 128 x 16 plans gained nothing: 1 (same paragraph)
+  if (A.pf_npad > 0 && !c.ep) grid = xcd_grid(grid * (sw.pf_rounds ? sw.pf_rounds : (T == 64 && !E->all_trio) ? 4 : 1));
+  const pmjit::FusedKernel* FK = (c.ep_only && !A.denovo && T == 64) ? fused_kernel(E) : nullptr;
+  if (FK) return launch_fused(E, FK, A, list);
+  if (c.ep) return launch_ep_chunks(E, fn, grid, T, shmem, A, list);
+  return launch_plain(E, fn, grid, T, shmem, A, list);
 }
 
 // The de novo Brent item of every called site of a vcf_mode batch (three-genotype mutation model, vcf_denovo_dev.h) and the
@@ -1253,14 +1091,10 @@ static int launch_vcf_denovo(pm_engine* E, const DevArgs& A) {
   V.terms = E->d_vdn_terms; V.n_terms = E->vdn_terms; V.n_peel = E->vdn_peel; V.n_nuc = E->vdn_nuc;
   V.co_lds = E->vdn_lds > 0; V.co = E->d_vdn_co; V.ws = E->d_vdn_ws;
   const int grid = std::max(1, std::min(E->vdn_grid, A.n));
-  hipEvent_t a, b;
-  HIP_TRY(hipEventCreate(&a));
-  HIP_TRY(hipEventCreate(&b));
-  E->brent_events.push_back({a, b});
-  HIP_TRY(hipEventRecord(a, E->stream));
+  if (int rc = mark(E, E->brent_events, true)) return rc;
   hipLaunchKernelGGL(E->vdn_T == 64 ? k_vdn_brent<64> : k_vdn_brent<256>, dim3(grid), dim3(E->vdn_T), E->vdn_lds, E->stream, A, V);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(b, E->stream));
+  if (int rc = mark(E, E->brent_events, false)) return rc;
   hipLaunchKernelGGL(k_finalize_vdn, dim3((A.n + 255) / 256), dim3(256), 0, E->stream, A);
   HIP_TRY(hipGetLastError());
   return PM_OK;
@@ -1291,7 +1125,7 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
     // sites per wave: PREP_SPW (PM_PREP_SPW = 1..8 overrides it; fewer sites per wave on config 4's 16 384-site
     // batches measured slower: 20.3 -> 19.7 M sites/s at 1, config 5 within noise, profiles/r05sp_ab_prep_spw.txt)
     int spw = PREP_SPW;
-    if (const char* s = getenv("PM_PREP_SPW"); s && *s) spw = std::max(1, std::min(PREP_SPW, atoi(s)));
+    if (E->sw.prep_spw) spw = std::min(PREP_SPW, E->sw.prep_spw);
     hipLaunchKernelGGL(prep, dim3((n + 4 * spw - 1) / (4 * spw)), dim3(256), 0, E->stream, A, spw);
   }
   HIP_TRY(hipGetLastError());
@@ -1362,7 +1196,7 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
       const size_t per = (size_t)E->ws_per_lane * sizeof(double);
       int bt = 0;
       for (int t : {256, 128, 64})
-        if (!bt && per * t <= 64 * 1024 && !getenv("PM_ES_POST_HBM")) bt = t;
+        if (!bt && per * t <= 64 * 1024 && !E->sw.es_post_hbm) bt = t;
       if (bt) {
         const int per_cu = std::max(1, (int)((160 * 1024) / (per * bt + 3 * 1024)));
         void (*pe)(DevArgs) = E->par.denovo ? k_posterior_es<true, true> : k_posterior_es<false, true>;
@@ -1396,23 +1230,19 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
 }
 
 static int collect_stats(pm_engine* E) {
-  for (auto& pr : E->brent_events) {
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, pr.first, pr.second));
-    E->stats.kernel_ms += ms;
-    E->stats.launches++;
-    hipEventDestroy(pr.first); hipEventDestroy(pr.second);
-  }
-  E->brent_events.clear();
-  for (auto& pr : E->es_events) {
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, pr.first, pr.second));
-    E->stats.es_hoist_ms += ms;
-    E->stats.es_hoist_launches++;
-    hipEventDestroy(pr.first); hipEventDestroy(pr.second);
-  }
-  E->es_events.clear();
-  return PM_OK;
+  auto drain = [](std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, auto& ms_sum, auto& launches) -> int {
+    for (auto& pr : v) {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, pr.first, pr.second));
+      ms_sum += ms;
+      launches++;
+      hipEventDestroy(pr.first); hipEventDestroy(pr.second);
+    }
+    v.clear();
+    return PM_OK;
+  };
+  if (int rc = drain(E->brent_events, E->stats.kernel_ms, E->stats.launches)) return rc;
+  return drain(E->es_events, E->stats.es_hoist_ms, E->stats.es_hoist_launches);
 }
 
 int pm_engine_run_device(pm_engine* E, int32_t n, const uint8_t* d_pl, const uint32_t* d_dm, const uint8_t* d_ref, pm_site_result* d_res,
@@ -1427,7 +1257,7 @@ int pm_engine_run_device(pm_engine* E, int32_t n, const uint8_t* d_pl, const uin
 static int finish_batch(pm_engine* E, const int* counts) {
   if (counts[4] != 0x7fffffff) E->carry_postprob = true;
   E->stats.items += (int64_t)counts[0] + counts[1] + counts[2] + counts[8];
-  E->stats.site_visits += (int64_t)counts[0] / (E->vcf ? 1 : (E->par.denovo && !mono_dn_in_prep(E)) ? 4 : 3) + counts[1] / 3 +
+  E->stats.site_visits += (int64_t)counts[0] / (E->vcf ? 1 : (E->par.denovo && !pmplan::mono_dn(facts_of(E), E->sw)) ? 4 : 3) + counts[1] / 3 +
                           counts[2] + counts[9];
   E->stats.sites += E->last_n;
   if (E->es_ops_known && (E->use_plan1 ? E->n_ext1 : E->n_ext) > 0) {
