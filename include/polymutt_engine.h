@@ -105,8 +105,10 @@ typedef struct {
  * describes them); setting or clearing one afterwards does not affect a live engine.  Among them:
  *   PM_NO_PREFETCH=1  the lean kernels hoist from direct HBM loads instead of LDS-staged PL bytes (tests
  *                     compare the two paths bit for bit);
- *   PM_BRENT_TS=T,S   force the Brent lane plan to T threads x S slots when it holds the pedigree
- *                     (tools/brent_sweep.py geometry sweeps). */
+ *   PM_BRENT_TS=T,S   force the Brent lane plan to T threads x S slots when it holds the pedigree (silently ignored
+ *                     when it does not: check pm_engine_plan).  tools/brent_sweep.py sweeps geometries with it, and
+ *                     tests/test_gpu_brent_variants.py launches every k_brent instantiation through it and compares
+ *                     each with the oracle; 31 instantiations are reached by no other means. */
 
 /* Objective-evaluation numerics.  All three compute CalcAllFamLogLikelihood; they differ in rounding only.
  *   PM_NUM_PRODUCT: each family's likelihood exactly as the reference forms it (same operations, same order),
@@ -190,6 +192,13 @@ void pm_engine_destroy(pm_engine *eng);
 /* The lane plan pm_engine_create chose for the Brent kernel: threads per item (one wave = 64) and
  * family slots per lane.  Diagnostics and tests only (no reference counterpart). */
 int pm_engine_plan(pm_engine *eng, int32_t *threads, int32_t *slots);
+
+/* The distinct k_brent instantiations this engine has enqueued since pm_engine_create, in first-launch order: 11
+ * int32 each, k_brent's template arguments in order (T, S, NUM, GEN, ES, DN, PF, EP, QD, NF, PD; brent_variants.h).
+ * At most `cap` of them are written to keys; *n receives their number even when it exceeds cap.  The fused
+ * hoisting + Brent kernel of all-peeled bi-allelic engines is no k_brent instantiation and is not listed.  Host
+ * bookkeeping only.  Diagnostics and tests only (no reference counterpart). */
+int pm_engine_brent_variants(pm_engine *eng, int32_t *keys, int32_t cap, int32_t *n);
 
 /* famlk[0]'s stale state across sites: whether CalcPostProb has already run earlier in the run (any
  * earlier site reached OutputVCF).  The reference's likelihoodONEKid reads the object's member `sex`

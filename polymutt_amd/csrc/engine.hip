@@ -106,6 +106,7 @@ struct pm_engine {
   int Tq = 0, Sq = 0, grid_q = 0;
   bool units_empty = false, units1_empty = false;   // a lane plan with no nuclear or founder unit (every family peeled)
   std::vector<std::pair<const void*, int>> bpc;   // QUAD / EP one-wave k_brent blocks resident per CU, per instantiation
+  std::vector<int> brent_launched;   // kBrentTable indices of the instantiations enqueued so far (pm_engine_brent_variants)
   bool all_trio = false;   // every unit of the lane plan is a 3-person nuclear family (or empty): k_brent's NF = 3
   bool split34 = false;    // plan_split34: quads in the first half of the slot rows, trios in the second (NF = 34)
   int4* d_units_q = nullptr;
@@ -756,6 +757,17 @@ int pm_engine_plan(pm_engine* E, int32_t* threads, int32_t* slots) {
   return PM_OK;
 }
 
+int pm_engine_brent_variants(pm_engine* E, int32_t* keys, int32_t cap, int32_t* n) {
+  if (!E || !n || cap < 0 || (cap > 0 && !keys)) { pm_set_last_error("pm_engine_brent_variants: invalid arguments"); return PM_EINVAL; }
+  *n = (int32_t)E->brent_launched.size();
+  for (int i = 0; i < std::min<int>(cap, *n); i++) {
+    const pmplan::BrentKey& k = kBrentTable[E->brent_launched[i]].key;
+    const int32_t v[11] = {k.T, k.S, k.NUM, k.GEN, k.ES, k.DN, k.PF, k.EP, k.QD, k.NF, k.PD};
+    std::copy(v, v + 11, keys + (size_t)i * 11);
+  }
+  return PM_OK;
+}
+
 int pm_engine_set_posterior_carry(pm_engine* E, int32_t seen) {
   if (!E) { pm_set_last_error("pm_engine_set_posterior_carry: invalid arguments"); return PM_EINVAL; }
   E->carry_postprob = seen != 0;
@@ -930,8 +942,11 @@ static int resident_blocks(pm_engine* E, BrentFn fn, int T, size_t lds) {
   return n;
 }
 
-// One k_brent launch between its pair of events.
+// One k_brent launch between its pair of events; the instantiation is noted for pm_engine_brent_variants.
 static int launch_plain(pm_engine* E, BrentFn fn, int grid, int T, size_t lds, const DevArgs& A, int list) {
+  for (int i = 0; i < (int)(sizeof(kBrentTable) / sizeof(kBrentTable[0])); i++)
+    if (kBrentTable[i].fn == fn && std::find(E->brent_launched.begin(), E->brent_launched.end(), i) == E->brent_launched.end())
+      E->brent_launched.push_back(i);
   if (int rc = mark(E, E->brent_events, true)) return rc;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(T), lds, E->stream, A, list);
   HIP_TRY(hipGetLastError());

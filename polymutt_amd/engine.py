@@ -111,6 +111,7 @@ EXPORTS = {
     "pm_engine_create": (i32, [P(PedigreeStruct), P(Params), i32, i32, P(C.c_void_p)]),
     "pm_engine_destroy": (None, [C.c_void_p]),
     "pm_engine_plan": (i32, [C.c_void_p, P(i32), P(i32)]),
+    "pm_engine_brent_variants": (i32, [C.c_void_p, P(i32), i32, P(i32)]),
     "pm_engine_set_posterior_carry": (i32, [C.c_void_p, i32]),
     "pm_engine_begin_section": (i32, [C.c_void_p, i32]),
     "pm_engine_run": (i32, [C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p, i32, C.c_void_p, C.c_void_p, P(i32)]),
@@ -357,6 +358,15 @@ class Engine:
         t, s = i32(0), i32(0)
         self._check(self.lib.pm_engine_plan(self.h, C.byref(t), C.byref(s)))
         return t.value, s.value
+
+    def brent_variants(self):
+        """pm_engine_brent_variants: the distinct k_brent instantiations launched so far, as 11-tuples of the template
+        arguments (T, S, NUM, GEN, ES, DN, PF, EP, QD, NF, PD), in first-launch order."""
+        n = i32(0)
+        self._check(self.lib.pm_engine_brent_variants(self.h, None, 0, C.byref(n)))
+        keys = (i32 * (11 * max(1, n.value)))()
+        self._check(self.lib.pm_engine_brent_variants(self.h, keys, n.value, C.byref(n)))
+        return [tuple(keys[11 * i:11 * i + 11]) for i in range(n.value)]
 
     def kernel_stats(self, reset=False):
         s = KernelStats()
