@@ -347,6 +347,51 @@ int pm_engine_denovo_carriers(pm_engine *eng, pm_person_dn *top, pm_person_dn *a
  * pm_engine_set_denovo_carriers keep refusing vcf_mode engines. */
 int pm_engine_set_vcf_denovo(pm_engine *eng, int32_t on);
 
+/* The families and the children behind each DQ of pm_engine_set_vcf_denovo (vcf_mode engines; additive to ABI 8: callers
+ * detect the feature by these symbols; no reference counterpart).  A row is a called site (status == 0) of an autosomal
+ * section with evals[2] > 0 and denovo_lr >= pm_params.denovo_min_llr; rows are numbered in ascending site order within
+ * the batch.  Everything is in the three states g = (g11, g12, g22) and the tables M3, T, Tdn above, the families routed
+ * and the founders given Hardy-Weinberg priors as for N.
+ *   Per family f:  D_f = log10 L_f^dn(x_N) - log10 L_f^std(x_D), x_N = varfreq[2], x_D = varfreq[1].  L_f^dn is the
+ *     family's factor of the de novo objective (a peeled family by the peel with Tdn, the FamilyLikelihoodES.cpp:1391
+ *     quirk included; a nuclear family by the closed form on D = M3 l; a founders-only family the product of its persons);
+ *     L_f^std is the same code with M3 = identity and plain T.  Sum_f D_f = denovo_lr up to summation rounding.  Each
+ *     log10 is taken of the whole double, so a family without data gives about -2e-8.
+ *   Per non-founder c (father fa, mother mo), at x_N in the de novo model:
+ *     pp    = Sum_{a,b in the 3 states} J_c(a, b, NonMend3(a, b)) / L_f^dn, J_c(a, b, S) = L_f^dn restricted to G_fa = a,
+ *             G_mo = b, G_c in S, NonMend3(a, b) = the states among the three that cannot take one allele from each
+ *             parent (empty for 12 x 12);
+ *     event = the pair (a, b) of the largest term, then the state of NonMend3(a, b) with the largest J_c(a, b, {s}); ties
+ *             go to the first in state order (a1a1, a1a2, a2a2); (-1, -1, -1) when every term is 0.
+ *     Genotypes are reported as GLF indices 0..9 (the values g[s]) in pm_person_dn; founders get (-1, -1, -1) and 0.0.  A
+ *     child reached only through a type-3 step with a marriage partial has pp = 0 (plain T there: the reference's model).
+ * Rankings: pm_fam_lr by D_f descending, ties by lower family index; persons by pp descending, ties by lower person
+ * index; padding entries as in the GLF features.  One block per row at a time (k_vdn_rows + k_vdn_who after the de novo
+ * item); fixed reduction trees and no floating-point atomics, so the same input gives the same bytes.  The site results
+ * and the genotype rows are those of pm_engine_set_vcf_denovo alone, byte for byte.
+ *
+ * fam_k, car_k: 0 (that half off) or 1..8 entries kept per row; both 0 switches the feature off and frees its buffers
+ * (the default: nothing is allocated or launched).  want_all != 0 also keeps the full [max_batch][n_fam] and
+ * [max_batch][n_person] matrices of the halves that are on (PM_EINVAL above 1 GiB each).
+ * PM_EINVAL: an engine without vcf_mode, pm_engine_set_vcf_denovo not on, k out of range, or a submitted batch not yet
+ * collected.  pm_engine_set_vcf_denovo(eng, 0) also switches this off.  pm_engine_set_denovo_families and
+ * pm_engine_set_denovo_carriers still refuse vcf_mode engines. */
+int pm_engine_set_vcf_denovo_detail(pm_engine *eng, int32_t fam_k, int32_t car_k, int32_t want_all);
+
+/* The rows of the last finished batch (after pm_engine_run, _run_vcf, _collect, or _run_device + _sync): *n_rows, and
+ * their batch indices in site[n_rows] (may be NULL).  0 rows with the feature off and on chrX/Y/MT sections.  After
+ * PM_EBRENT only the rows before the stuck site are counted and valid.  Like the two readers below, PM_EINVAL while a
+ * submitted batch has not been collected. */
+int pm_engine_vcf_denovo_rows(pm_engine *eng, int32_t *n_rows, int32_t *site);
+
+/* top[n_rows][fam_k] (entries past n_fam are {fam = -1, lr = 0}), sum[n_rows] (Sum_f D_f; may be NULL) and
+ * all[n_rows][n_fam] (may be NULL; PM_EINVAL when asked for without want_all).  PM_EINVAL with fam_k == 0. */
+int pm_engine_vcf_denovo_families(pm_engine *eng, pm_fam_lr *top, double *sum, double *all);
+
+/* top[n_rows][car_k] (entries past the non-founder count are {-1, -1, -1, -1, 0, 0.0}) and all[n_rows][n_person]
+ * (person = p; may be NULL; PM_EINVAL when asked for without want_all).  PM_EINVAL with car_k == 0. */
+int pm_engine_vcf_denovo_carriers(pm_engine *eng, pm_person_dn *top, pm_person_dn *all);
+
 /* Page-locked host memory for pm_engine_submit's inputs and the result rows (H2D/D2H at full PCIe rate). */
 int pm_host_alloc(uint64_t bytes, void **h_ptr);
 int pm_host_free(void *h_ptr);

@@ -135,6 +135,17 @@ struct pm_engine {
   size_t vdn_lds = 0;        // dynamic LDS of k_vdn_brent (the hoisted coefficients), 0: they live in d_vdn_co
   int* d_vdn_terms = nullptr;
   double *d_vdn_co = nullptr, *d_vdn_ws = nullptr;
+  // the families and children behind each DQ (pm_engine_set_vcf_denovo_detail): off (both k 0) = no buffer, no launch
+  int vw_fam_k = 0, vw_car_k = 0, vw_grid = 0, vw_n_nuc = 0, vw_n_es = 0;
+  int vw_rows = 0;            // rows of the last finished batch (after PM_EBRENT: those before the stuck site)
+  int* d_vw_row_site = nullptr;                                         // [max_batch]
+  int* d_vw_pfam = nullptr;                                             // [n_person]
+  pm_fam_lr* d_vw_fam_top = nullptr;                                    // [max_batch][fam_k]
+  double *d_vw_fam_sum = nullptr, *d_vw_fam_all = nullptr, *d_vw_fam_line = nullptr;   // [max_batch], [max_batch][n_fam] | [vw_grid][n_fam]
+  pm_person_dn *d_vw_car_top = nullptr, *d_vw_car_all = nullptr, *d_vw_car_line = nullptr;   // [max_batch][car_k], [max_batch][n_person] | [vw_grid][n_person]
+  int2* d_vw_kids = nullptr;
+  int8_t* d_vw_is_kid = nullptr;
+  double* d_vw_jbuf = nullptr;                                          // [vw_grid][vw_n_es * 13]
   std::vector<int> fam_kind_h, fam_perm_h;
   std::vector<int32_t> fa_h, mo_h;  // family-local parent indices (-1: none)
   unsigned long long* d_counters = nullptr;
@@ -355,7 +366,9 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_items[0], E->d_items[1], E->d_items[2], E->d_counts, E->d_eval_total, E->d_row_site,
                   E->d_counters, E->d_row_blk, E->d_qctr, E->d_fam_top, E->d_fam_sum, E->d_fam_all, E->d_fam_line,
                   E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf,
-                  E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws};
+                  E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws, E->d_vw_row_site, E->d_vw_pfam, E->d_vw_fam_top, E->d_vw_fam_sum,
+                  E->d_vw_fam_all, E->d_vw_fam_line, E->d_vw_car_top, E->d_vw_car_all, E->d_vw_car_line, E->d_vw_kids, E->d_vw_is_kid,
+                  E->d_vw_jbuf};
   for (void* b : bufs) if (b) hipFree(b);
   for (auto& pl : E->d_jit_slots)
     for (int* b : pl) if (b) hipFree(b);
@@ -1112,6 +1125,19 @@ static int launch_vcf_denovo(pm_engine* E, const DevArgs& A) {
   if (int rc = mark(E, E->brent_events, false)) return rc;
   hipLaunchKernelGGL(k_finalize_vdn, dim3((A.n + 255) / 256), dim3(256), 0, E->stream, A);
   HIP_TRY(hipGetLastError());
+  if (E->vw_fam_k > 0 || E->vw_car_k > 0) {   // the rows (DQ at or above the threshold), then their families and children
+    VdnWhoArgs W;
+    W.fam_k = E->vw_fam_k; W.car_k = E->vw_car_k; W.row_site = E->d_vw_row_site;
+    W.fam_top = E->d_vw_fam_top; W.fam_sum = E->d_vw_fam_sum; W.fam_all = E->d_vw_fam_all; W.fam_line = E->d_vw_fam_line;
+    W.pfam = E->d_vw_pfam; W.car_top = E->d_vw_car_top; W.car_all = E->d_vw_car_all; W.car_line = E->d_vw_car_line;
+    W.kids = E->d_vw_kids; W.n_nuc = E->vw_n_nuc; W.n_es = E->vw_n_es; W.is_kid = E->d_vw_is_kid; W.jbuf = E->d_vw_jbuf;
+    hipLaunchKernelGGL(k_vdn_rows, dim3(1), dim3(1024), 0, E->stream, A, E->d_vw_row_site);
+    HIP_TRY(hipGetLastError());
+    // (blocks beyond the row count leave at once; the peel workspace is k_vdn_brent's, sized for vdn_grid >= vw_grid blocks)
+    const int wgrid = std::max(1, std::min(E->vw_grid, A.n));
+    hipLaunchKernelGGL(E->vdn_T == 64 ? k_vdn_who<64> : k_vdn_who<256>, dim3(wgrid), dim3(E->vdn_T), 0, E->stream, A, V, W);
+    HIP_TRY(hipGetLastError());
+  }
   return PM_OK;
 }
 
@@ -1289,6 +1315,15 @@ static int finish_batch(pm_engine* E, const int* counts) {
   if (rc) return rc;
   E->stuck_site = counts[5] ? counts[6] : -1;
   E->last_rows = counts[3];
+  E->vw_rows = 0;
+  if (E->vw_fam_k > 0 || E->vw_car_k > 0) {
+    E->vw_rows = counts[10];
+    if (counts[5] && E->vw_rows > 0) {   // a stuck site: only the rows before it are valid (rows are in site order)
+      std::vector<int> rs((size_t)E->vw_rows);
+      HIP_TRY(hipMemcpy(rs.data(), E->d_vw_row_site, sizeof(int) * rs.size(), hipMemcpyDeviceToHost));
+      E->vw_rows = (int)(std::lower_bound(rs.begin(), rs.end(), counts[6]) - rs.begin());
+    }
+  }
   if (counts[5]) { pm_set_last_error("ScalarMinimizer::Brent got stuck"); return PM_EBRENT; }
   return PM_OK;
 }
@@ -1323,6 +1358,16 @@ int pm_engine_set_denovo_families(pm_engine* E, int32_t top_k, int32_t want_all)
   return PM_OK;
 }
 
+// pm_engine_set_vcf_denovo_detail's buffers (the stream is idle)
+static void vw_free(pm_engine* E) {
+  E->vw_fam_k = E->vw_car_k = 0;
+  E->vw_rows = 0;
+  void** bufs[] = {(void**)&E->d_vw_row_site, (void**)&E->d_vw_pfam, (void**)&E->d_vw_fam_top, (void**)&E->d_vw_fam_sum, (void**)&E->d_vw_fam_all,
+                   (void**)&E->d_vw_fam_line, (void**)&E->d_vw_car_top, (void**)&E->d_vw_car_all, (void**)&E->d_vw_car_line,
+                   (void**)&E->d_vw_kids, (void**)&E->d_vw_is_kid, (void**)&E->d_vw_jbuf};
+  for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+}
+
 int pm_engine_set_vcf_denovo(pm_engine* E, int32_t on) {
   if (!E) { pm_set_last_error("pm_engine_set_vcf_denovo: invalid arguments"); return PM_EINVAL; }
   if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_denovo: the engine was created without vcf_mode"); return PM_EINVAL; }
@@ -1332,7 +1377,7 @@ int pm_engine_set_vcf_denovo(pm_engine* E, int32_t on) {
   E->vdn_on = false;
   void** bufs[] = {(void**)&E->d_vdn_terms, (void**)&E->d_vdn_co, (void**)&E->d_vdn_ws};
   for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
-  if (!on) return PM_OK;
+  if (!on) { vw_free(E); return PM_OK; }
   // the objective's terms, routed like the vcf_mode objective: peeled families (every family with offspring when the
   // pedigree is one family, the extended ones otherwise), nuclear families in closed form, founder persons
   std::vector<int> peel, nuc, pers;
@@ -1371,6 +1416,119 @@ int pm_engine_set_vcf_denovo(pm_engine* E, int32_t on) {
     return rc;
   HIP_TRY(hipMemcpy(E->d_vdn_terms, terms.data(), sizeof(int) * terms.size(), hipMemcpyHostToDevice));
   E->vdn_on = true;
+  return PM_OK;
+}
+
+int pm_engine_set_vcf_denovo_detail(pm_engine* E, int32_t fam_k, int32_t car_k, int32_t want_all) {
+  if (!E) { pm_set_last_error("pm_engine_set_vcf_denovo_detail: invalid arguments"); return PM_EINVAL; }
+  if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_denovo_detail: the engine was created without vcf_mode"); return PM_EINVAL; }
+  if (fam_k < 0 || fam_k > 8 || car_k < 0 || car_k > 8) {
+    pm_set_last_error("pm_engine_set_vcf_denovo_detail: fam_k and car_k must each be 0 (off) or 1..8");
+    return PM_EINVAL;
+  }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_vcf_denovo_detail: a submitted batch has not been collected"); return PM_EINVAL; }
+  if ((fam_k > 0 || car_k > 0) && !E->vdn_on) {
+    pm_set_last_error("pm_engine_set_vcf_denovo_detail: needs pm_engine_set_vcf_denovo(engine, 1) first (vcf_denovo is off)");
+    return PM_EINVAL;
+  }
+  const size_t nb = (size_t)E->max_batch, nf = (size_t)E->n_fam, np = (size_t)E->n_person;
+  if (want_all && ((fam_k > 0 && nb * nf * sizeof(double) > ((size_t)1 << 30)) || (car_k > 0 && nb * np * sizeof(pm_person_dn) > ((size_t)1 << 30)))) {
+    char b[320];
+    snprintf(b, sizeof(b), "pm_engine_set_vcf_denovo_detail: want_all needs max_batch x n_fam x 8 = %zu and max_batch x n_person x 16 = %zu bytes "
+             "on the device (limit 1 GiB each)", nb * nf * sizeof(double), nb * np * sizeof(pm_person_dn));
+    pm_set_last_error(b);
+    return PM_EINVAL;
+  }
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  vw_free(E);
+  if (fam_k == 0 && car_k == 0) return PM_OK;
+  // the children: every person with both parents in the family, of the closed-form nuclear families (k_vdn_brent's
+  // routing: n_fam > 1), then of the peeled ones
+  std::vector<int2> kids, kids_es;
+  std::vector<int8_t> is_kid(np, 0);
+  std::vector<int> pfam(np, 0);
+  for (int f = 0; f < E->n_fam; f++) {
+    const int kind = E->fam_kind_h[f], p0 = E->fam_start_h[f], n = E->fam_start_h[f + 1] - p0;
+    for (int j = 0; j < n; j++) pfam[p0 + j] = f;
+    if (kind == PM_FAM_FOUNDERS) continue;
+    const bool closed = kind == PM_FAM_NUCLEAR && E->n_fam > 1;
+    for (int j = 0; j < n; j++) {
+      const int fa = E->fa_h[p0 + j], mo = E->mo_h[p0 + j];
+      if (fa < 0 || mo < 0 || fa >= n || mo >= n || fa == mo) continue;
+      if (closed && (j < 2 || fa > 1 || mo > 1)) continue;   // (a nuclear family is father, mother, kids)
+      (closed ? kids : kids_es).push_back(make_int2(f, j));
+      is_kid[p0 + j] = 1;
+    }
+  }
+  const int n_nuc = (int)kids.size(), n_es = (int)kids_es.size();
+  kids.insert(kids.end(), kids_es.begin(), kids_es.end());
+  // one block per row at a time, on k_vdn_brent's workspace (vdn_grid blocks); the peeled children's term buffer caps the
+  // grid at 256 MiB
+  int grid = E->vdn_grid;
+  const size_t per_block = (size_t)n_es * 13 * sizeof(double);
+  if (per_block) grid = (int)std::max<size_t>(1, std::min<size_t>(grid, ((size_t)1 << 28) / per_block));
+  int rc;
+  if ((rc = dalloc(&E->d_vw_row_site, nb)) || (rc = dalloc(&E->d_vw_pfam, np)) || (rc = dalloc(&E->d_vw_kids, kids.size())) ||
+      (rc = dalloc(&E->d_vw_is_kid, np)))
+    { vw_free(E); return rc; }
+  if (fam_k > 0) {
+    if ((rc = dalloc(&E->d_vw_fam_top, nb * fam_k)) || (rc = dalloc(&E->d_vw_fam_sum, nb)) ||
+        (rc = want_all ? dalloc(&E->d_vw_fam_all, nb * nf) : dalloc(&E->d_vw_fam_line, (size_t)grid * nf)))
+      { vw_free(E); return rc; }
+  }
+  if (car_k > 0) {
+    if ((rc = dalloc(&E->d_vw_car_top, nb * car_k)) ||
+        (rc = want_all ? dalloc(&E->d_vw_car_all, nb * np) : dalloc(&E->d_vw_car_line, (size_t)grid * np)) ||
+        (per_block && (rc = dalloc(&E->d_vw_jbuf, (size_t)grid * n_es * 13))))
+      { vw_free(E); return rc; }
+  }
+  HIP_TRY(hipMemcpy(E->d_vw_pfam, pfam.data(), sizeof(int) * np, hipMemcpyHostToDevice));
+  if (!kids.empty()) HIP_TRY(hipMemcpy(E->d_vw_kids, kids.data(), sizeof(int2) * kids.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(E->d_vw_is_kid, is_kid.data(), np, hipMemcpyHostToDevice));
+  E->vw_grid = grid; E->vw_n_nuc = n_nuc; E->vw_n_es = n_es;
+  E->vw_fam_k = fam_k; E->vw_car_k = car_k;
+  return PM_OK;
+}
+
+int pm_engine_vcf_denovo_rows(pm_engine* E, int32_t* n_rows, int32_t* site) {
+  if (!E || !n_rows) { pm_set_last_error("pm_engine_vcf_denovo_rows: invalid arguments"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_vcf_denovo_rows: a submitted batch has not been collected"); return PM_EINVAL; }
+  *n_rows = (E->vw_fam_k > 0 || E->vw_car_k > 0) ? E->vw_rows : 0;
+  if (site && *n_rows > 0) {
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipMemcpy(site, E->d_vw_row_site, sizeof(int32_t) * (size_t)*n_rows, hipMemcpyDeviceToHost));
+  }
+  return PM_OK;
+}
+
+int pm_engine_vcf_denovo_families(pm_engine* E, pm_fam_lr* top, double* sum, double* all) {
+  if (!E || !top) { pm_set_last_error("pm_engine_vcf_denovo_families: invalid arguments"); return PM_EINVAL; }
+  if (E->vw_fam_k <= 0) { pm_set_last_error("pm_engine_vcf_denovo_families: the feature is off (pm_engine_set_vcf_denovo_detail fam_k)"); return PM_EINVAL; }
+  if (all && !E->d_vw_fam_all) { pm_set_last_error("pm_engine_vcf_denovo_families: the full matrix needs want_all"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_vcf_denovo_families: a submitted batch has not been collected"); return PM_EINVAL; }
+  const size_t rows = (size_t)E->vw_rows;
+  if (rows == 0) return PM_OK;
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  HIP_TRY(hipMemcpy(top, E->d_vw_fam_top, sizeof(pm_fam_lr) * rows * E->vw_fam_k, hipMemcpyDeviceToHost));
+  if (sum) HIP_TRY(hipMemcpy(sum, E->d_vw_fam_sum, sizeof(double) * rows, hipMemcpyDeviceToHost));
+  if (all) HIP_TRY(hipMemcpy(all, E->d_vw_fam_all, sizeof(double) * rows * E->n_fam, hipMemcpyDeviceToHost));
+  return PM_OK;
+}
+
+int pm_engine_vcf_denovo_carriers(pm_engine* E, pm_person_dn* top, pm_person_dn* all) {
+  if (!E || !top) { pm_set_last_error("pm_engine_vcf_denovo_carriers: invalid arguments"); return PM_EINVAL; }
+  if (E->vw_car_k <= 0) { pm_set_last_error("pm_engine_vcf_denovo_carriers: the feature is off (pm_engine_set_vcf_denovo_detail car_k)"); return PM_EINVAL; }
+  if (all && !E->d_vw_car_all) { pm_set_last_error("pm_engine_vcf_denovo_carriers: the full matrix needs want_all"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_vcf_denovo_carriers: a submitted batch has not been collected"); return PM_EINVAL; }
+  const size_t rows = (size_t)E->vw_rows;
+  if (rows == 0) return PM_OK;
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  HIP_TRY(hipMemcpy(top, E->d_vw_car_top, sizeof(pm_person_dn) * rows * E->vw_car_k, hipMemcpyDeviceToHost));
+  if (all) HIP_TRY(hipMemcpy(all, E->d_vw_car_all, sizeof(pm_person_dn) * rows * E->n_person, hipMemcpyDeviceToHost));
   return PM_OK;
 }
 
@@ -1525,7 +1683,7 @@ int pm_engine_collect(pm_engine* E, pm_site_result* res, pm_geno_call* calls, in
   const int n = E->pending_n;
   E->pending_n = -1;
   *n_rows = 0;
-  if (n == 0) { E->last_rows = 0; return PM_OK; }
+  if (n == 0) { E->last_rows = 0; E->vw_rows = 0; return PM_OK; }
   HIP_TRY(hipSetDevice(E->device));
   HIP_TRY(hipStreamSynchronize(E->stream));
   int counts[16];
@@ -1580,7 +1738,7 @@ int pm_engine_run(pm_engine* E, int32_t n, const uint8_t* pl, const uint32_t* dm
                   pm_site_result* res, pm_geno_call* calls, int32_t* n_rows) {
   if (!E || n < 0 || n > E->max_batch || !res || !n_rows) { pm_set_last_error("pm_engine_run: invalid arguments"); return PM_EINVAL; }
   *n_rows = 0;
-  if (n == 0) { E->last_rows = 0; return PM_OK; }
+  if (n == 0) { E->last_rows = 0; E->vw_rows = 0; return PM_OK; }
   if (!on_device) {   // host inputs: submit + collect
     int rc = pm_engine_submit(E, n, pl, dm, ref);
     if (rc) { E->pending_n = -1; return rc; }

@@ -29,8 +29,13 @@ struct VdnArgs {
 };
 
 // d_es_lk<3> on an autosome with the transmission tables passed in (LDS): tdn where the de novo model mutates, tba elsewhere
+// CL: three more persons c0, c1, c2 (family-local indices) are clamped to the state sets m0, m1, m2 (bit s = state s of
+// (g11, g12, g22) allowed), where the initial partials are filled, as d_es_lk<10, true> does (k_vdn_who); without CL
+// nothing is added.
+template <bool CL = false>
 __device__ __forceinline__ double d_es_lk3_vdn(const DevArgs& A, int f, const uint8_t* pl, const double* lk, const int* gidx, double freq,
-                                               const double* tdn, const double* tba, double* ws, size_t st) {
+                                               const double* tdn, const double* tba, double* ws, size_t st, int c0 = -1, int m0 = 0,
+                                               int c1 = -1, int m1 = 0, int c2 = -1, int m2 = 0) {
   const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0, nf = A.fam_founders[f];
 #define PP(i, j) ws[((size_t)(i) * 3 + (j)) * st]
 #define MPP(sl, x, y) ws[((size_t)n * 3 + (size_t)(sl) * 9 + (x) * 3 + (y)) * st]
@@ -42,7 +47,9 @@ __device__ __forceinline__ double d_es_lk3_vdn(const DevArgs& A, int f, const ui
     if (i < nf) { pr[0] = freq * freq; pr[1] = 2 * freq * (1 - freq); pr[2] = (1 - freq) * (1 - freq); }
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-      const double pen = lk[R[gidx[j] * np]];
+      double pen = lk[R[gidx[j] * np]];
+      if (CL)
+        if ((i == c0 && !((m0 >> j) & 1)) || (i == c1 && !((m1 >> j) & 1)) || (i == c2 && !((m2 >> j) & 1))) pen = 0.0;
       PP(i, j) = fo ? pr[j] * pen : pen;
     }
   }
@@ -259,4 +266,379 @@ __global__ void __launch_bounds__(256) k_finalize_vdn(DevArgs A) {
   R->varfreq[2] = A.minv[site * 8 + 2];
   R->evals[2] = A.evals[site * 8 + 2];
   R->denovo_lr = N - A.raw[(size_t)site * 8 + 3];
+}
+
+// ------------------------------------------------------------------------------------------------
+// The families and the children behind each DQ (pm_engine_set_vcf_denovo_detail).  A row is a called site with
+// evals[2] > 0 (the de novo item ran) and denovo_lr >= pm_params.denovo_min_llr; rows are numbered in site order.
+struct VdnWhoArgs {
+  int fam_k, car_k;         // 0 (that half is off) or 1..8
+  int* row_site;            // [max_batch] row -> site (k_vdn_rows; the row count goes to counts[10])
+  pm_fam_lr* fam_top;       // [rows][fam_k]
+  double* fam_sum;          // [rows]
+  double* fam_all;          // [rows][n_fam], or null
+  double* fam_line;         // [gridDim.x][n_fam] when fam_all is null
+  const int* pfam;          // [n_person] the person's family
+  pm_person_dn* car_top;    // [rows][car_k]
+  pm_person_dn* car_all;    // [rows][n_person], or null
+  pm_person_dn* car_line;   // [gridDim.x][n_person] when car_all is null
+  const int2* kids;         // the non-founders {family, member}: n_nuc of closed-form nuclear families, then n_es of peeled ones
+  int n_nuc, n_es;
+  const int8_t* is_kid;     // [n_person] 1 = listed in kids
+  double* jbuf;             // [gridDim.x][n_es * 13] clamped-peel values: 9 pairs, 3 single states, L_f
+};
+
+// Rows in site order: one block walks the batch in 1024-site pieces, an exclusive scan per piece, so the table is the same
+// on every run.
+__global__ void __launch_bounds__(1024) k_vdn_rows(DevArgs A, int* row_site) {
+  __shared__ int s_w[16];
+  int base = 0;
+  for (int s0 = 0; s0 < A.n; s0 += 1024) {   // (block-uniform)
+    const int site = s0 + threadIdx.x;
+    int e = 0;
+    if (site < A.n) {
+      const pm_site_result* R = A.res + site;
+      e = (R->status == PM_SITE_CALLED && R->evals[2] > 0 && R->denovo_lr >= A.denovo_min_llr) ? 1 : 0;
+    }
+    int total;
+    const int pre = block_excl_scan_1024(e, s_w, total);
+    if (e) row_site[base + pre] = site;
+    base += total;
+    __syncthreads();   // (s_w is rewritten by the next piece)
+  }
+  if (threadIdx.x == 0) A.counts[10] = base;
+}
+
+// log10 of m 2^e taken of the whole double where it is one (vdn_logprod's rule: a family without data gives ~-2e-8)
+__device__ __forceinline__ double vdn_log10_me(double m, int e) {
+  if (e >= -1 && e <= 1) return log10(ldexp(m, e));
+  return log10(m) + e * 0.30102999566398119521;
+}
+
+// A nuclear family's closed form at the parental priors pp (d_parent_prior(PR_AUTO)): k_vdn_brent's hoisting, pass DN
+template <bool DN>
+__device__ __forceinline__ double vdn_nuc_lk(const uint8_t* P, size_t np, int n, const int* gidx, const double* lk, const double* m3,
+                                             const double* pp) {
+  double lF[3], lM[3], kids[9];
+#pragma unroll
+  for (int j = 0; j < 3; j++) { lF[j] = lk[P[gidx[j] * np]]; lM[j] = lk[P[gidx[j] * np + 1]]; }
+#pragma unroll
+  for (int k = 0; k < 9; k++) kids[k] = 1.0;
+  for (int j = 2; j < n; j++) {
+    const double l0 = lk[P[gidx[0] * np + j]], l1 = lk[P[gidx[1] * np + j]], l2 = lk[P[gidx[2] * np + j]];
+    const double D11 = DN ? m3[0] * l0 + m3[1] * l1 + m3[2] * l2 : l0;
+    const double D12 = DN ? m3[3] * l0 + m3[4] * l1 + m3[5] * l2 : l1;
+    const double D22 = DN ? m3[6] * l0 + m3[7] * l1 + m3[8] * l2 : l2;
+#pragma unroll
+    for (int k = 0; k < 9; k++) kids[k] *= d_one_kid_dn(k, D11, D12, D22);
+  }
+  double v = 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = 0; b < 3; b++) v += (kids[3 * a + b] * (lF[a] * lM[b])) * pp[3 * a + b];
+  return v;
+}
+
+// the family of term q of the VdnArgs list, -1 for a founder person that is not its family's first (that person's term
+// carries the whole founders-only family, summed in person order)
+__device__ __forceinline__ int vdn_term_fam(const DevArgs& A, const VdnArgs& V, const VdnWhoArgs& W, int q) {
+  const int x = V.terms[q];
+  if (q < V.n_peel + V.n_nuc) return x;
+  const int f = W.pfam[x];
+  return x == A.fam_start[f] ? f : -1;
+}
+
+__device__ __forceinline__ int vdn_pick3(const int* g, int s) { return s == 0 ? g[0] : s == 1 ? g[1] : g[2]; }
+
+// k_vdn_who: per row, in the three states of the record's (ref, alt) and the model of k_vdn_brent,
+//   D_f = log10 L_f^dn(varfreq[2]) - log10 L_f^std(varfreq[1]) of every family (k_vdn_brent's factors, pass 1 and pass 0),
+//   pp_c = Sum_{a,b} J_c(a, b, NonMend3(a, b)) / L_f^dn and the event of every non-founder c (k_person_dn's definitions),
+// and their top-k rankings.  One block of T threads per row at a time, after k_finalize_vdn on the engine's stream (the
+// peel workspace is k_vdn_brent's).  Families: the terms round robin over the threads.  Children of closed-form nuclear
+// families: one lane per child, registers only.  Children of peeled families: stage A, per (child, a, b) the peel with
+// father, mother and child clamped to a, b and NonMend3(a, b) (nothing for 12 x 12: the set is empty); stage B, per child
+// the unclamped L_f and the best pair's peels with the child clamped to one state; stage C, one thread per child sums the
+// nine terms in (a, b) order.  Barriers between the stages.  Sums and rankings are k_fam_dnlr's fixed trees: no atomics.
+template <int T>
+__global__ void __launch_bounds__(T) k_vdn_who(DevArgs A, VdnArgs V, VdnWhoArgs W) {
+  constexpr int NW = T / 64;
+  __shared__ double s_lk[256];
+  __shared__ double s_tba[27], s_tdn[27], s_m3[9];
+  __shared__ double s_red[2][4];
+  __shared__ int s_redf[2][4];
+  for (int i = threadIdx.x; i < 256; i += T) s_lk[i] = A.lktab[i];
+  if (threadIdx.x < 27) s_tba[threadIdx.x] = c_TBA[0][threadIdx.x];
+  const int rows = A.counts[10], nf = A.n_fam, nk = W.n_nuc + W.n_es;
+  const size_t np = (size_t)A.n_person;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  double* ws = V.ws + (size_t)blockIdx.x * A.ws_per_lane * T + threadIdx.x;
+  double* jb = W.jbuf + (size_t)blockIdx.x * W.n_es * 13;
+  int par = 0;
+  for (int row = blockIdx.x; row < rows; row += gridDim.x) {   // (block-uniform: every thread reaches the barriers)
+    const int site = W.row_site[row];
+    const pm_site_result* R = A.res + site;
+    const int r = A.ref[site];
+    const int a1 = r & 15, a2 = r >> 4;
+    const int gidx[3] = {d_gi(a1, a1), d_gi(a1, a2), d_gi(a2, a2)};
+    const uint8_t* pl = A.pl + (size_t)site * np * 10;
+    const double xN = R->varfreq[2], xD = R->varfreq[1];
+    __syncthreads();   // (the previous row no longer reads the tables, the lines or jbuf)
+    if (threadIdx.x < 9) s_m3[threadIdx.x] = A.M[vdn_pick3(gidx, threadIdx.x / 3) * 10 + vdn_pick3(gidx, threadIdx.x % 3)];
+    __syncthreads();
+    if (threadIdx.x < 27) {
+      const int ij = threadIdx.x / 3, k = threadIdx.x % 3;
+      double s = 0.0;
+      for (int m = 0; m < 3; m++) s += s_tba[ij * 3 + m] * s_m3[m * 3 + k];
+      s_tdn[threadIdx.x] = s;
+    }
+    __syncthreads();
+    double ppN[9];
+    d_parent_prior(PR_AUTO, xN, ppN);
+    if (W.fam_k > 0) {
+      double ppD[9];
+      d_parent_prior(PR_AUTO, xD, ppD);
+      double* line = W.fam_all ? W.fam_all + (size_t)row * nf : W.fam_line + (size_t)blockIdx.x * nf;
+      double part = 0.0;
+      for (int q = threadIdx.x; q < V.n_terms; q += T) {
+        const int f = vdn_term_fam(A, V, W, q);
+        if (f < 0) continue;
+        const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0;
+        double l_dn, l_std;
+        if (q < V.n_peel) {
+          l_dn = log10(d_es_lk3_vdn(A, f, pl, s_lk, gidx, xN, s_tdn, s_tba, ws, T));
+          l_std = log10(d_es_lk3_vdn(A, f, pl, s_lk, gidx, xD, s_tba, s_tba, ws, T));
+        } else if (q < V.n_peel + V.n_nuc) {
+          l_dn = log10(vdn_nuc_lk<true>(pl + p0, np, n, gidx, s_lk, s_m3, ppN));
+          l_std = log10(vdn_nuc_lk<false>(pl + p0, np, n, gidx, s_lk, s_m3, ppD));
+        } else {   // founders only: the product of lkSinglePerson, the same form in both models
+          double mN = 1.0, mD = 1.0;
+          int eN = 0, eD = 0;
+          const double gN = 1 - xN, gD = 1 - xD;
+          for (int j = 0; j < n; j++) {
+            const uint8_t* P = pl + p0 + j;
+            const double l11 = s_lk[P[gidx[0] * np]], l12 = s_lk[P[gidx[1] * np]], l22 = s_lk[P[gidx[2] * np]];
+            int e1;
+            mN = frexp(mN * (l11 * (xN * xN) + l12 * (2 * xN * gN) + l22 * (gN * gN)), &e1);
+            eN += e1;
+            mD = frexp(mD * (l11 * (xD * xD) + l12 * (2 * xD * gD) + l22 * (gD * gD)), &e1);
+            eD += e1;
+          }
+          l_dn = vdn_log10_me(mN, eN);
+          l_std = vdn_log10_me(mD, eD);
+        }
+        const double D = l_dn - l_std;
+        line[f] = D;
+        part += D;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+      if (lane == 0) s_red[par][wv] = part;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        double s = s_red[par][0];
+#pragma unroll
+        for (int w = 1; w < NW; w++) s += s_red[par][w];
+        W.fam_sum[row] = s;
+      }
+      par ^= 1;
+      double prev_lr = 0.0;
+      int prev_f = -1;
+      for (int k = 0; k < W.fam_k; k++) {   // round k takes the best entry that comes after round k - 1's in the order
+        double bl = 0.0;
+        int bf = INT_MAX;
+        for (int q = threadIdx.x; q < V.n_terms; q += T) {
+          const int f = vdn_term_fam(A, V, W, q);
+          if (f < 0) continue;
+          const double d = line[f];   // (written by this thread above)
+          const bool after = k == 0 ? d == d : (d < prev_lr || (d == prev_lr && f > prev_f));
+          if (after && fam_lr_before(d, f, bl, bf)) { bl = d; bf = f; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const double ol = __shfl_xor(bl, o, 64);
+          const int of = __shfl_xor(bf, o, 64);
+          if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
+        }
+        if (lane == 0) { s_red[par][wv] = bl; s_redf[par][wv] = bf; }
+        __syncthreads();
+        bl = s_red[par][0]; bf = s_redf[par][0];
+#pragma unroll
+        for (int w = 1; w < NW; w++)
+          if (fam_lr_before(s_red[par][w], s_redf[par][w], bl, bf)) { bl = s_red[par][w]; bf = s_redf[par][w]; }
+        par ^= 1;
+        if (threadIdx.x == 0) {
+          pm_fam_lr o;
+          o.fam = bf == INT_MAX ? -1 : bf; o.pad = 0; o.lr = bf == INT_MAX ? 0.0 : bl;
+          W.fam_top[(size_t)row * W.fam_k + k] = o;
+        }
+        if (bf == INT_MAX) { prev_lr = -INFINITY; prev_f = INT_MAX; }   // exhausted: every later round is empty too
+        else { prev_lr = bl; prev_f = bf; }
+      }
+    }
+    if (W.car_k > 0) {
+      pm_person_dn* line = W.car_all ? W.car_all + (size_t)row * np : W.car_line + (size_t)blockIdx.x * np;
+      for (int p = threadIdx.x; p < (int)np; p += T)   // founders (and anyone without both parents): no value
+        if (!W.is_kid[p]) {
+          pm_person_dn o;
+          o.person = p; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
+          line[p] = o;
+        }
+      // ---- closed-form nuclear families: one child per lane
+      for (int ci = threadIdx.x; ci < W.n_nuc; ci += T) {
+        const int2 kd = W.kids[ci];
+        const int p0 = A.fam_start[kd.x], n = A.fam_start[kd.x + 1] - p0, jc = kd.y;
+        const bool sw = A.fa_local[p0 + jc] == 1;   // (the closed form's first parent is person p0: the father unless the family lists the mother first)
+        const uint8_t* P = pl + p0;
+        double lF[3], lM[3], w[9];   // w: the family around c -- every other kid's factor, the parents, the prior
+#pragma unroll
+        for (int j = 0; j < 3; j++) { lF[j] = s_lk[P[gidx[j] * np]]; lM[j] = s_lk[P[gidx[j] * np + 1]]; }
+#pragma unroll
+        for (int k = 0; k < 9; k++) w[k] = 1.0;
+        for (int j = 2; j < n; j++) {
+          if (j == jc) continue;
+          const double l0 = s_lk[P[gidx[0] * np + j]], l1 = s_lk[P[gidx[1] * np + j]], l2 = s_lk[P[gidx[2] * np + j]];
+          const double D11 = s_m3[0] * l0 + s_m3[1] * l1 + s_m3[2] * l2;
+          const double D12 = s_m3[3] * l0 + s_m3[4] * l1 + s_m3[5] * l2;
+          const double D22 = s_m3[6] * l0 + s_m3[7] * l1 + s_m3[8] * l2;
+#pragma unroll
+          for (int k = 0; k < 9; k++) w[k] *= d_one_kid_dn(k, D11, D12, D22);
+        }
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+          for (int b = 0; b < 3; b++) w[3 * a + b] = (w[3 * a + b] * (lF[a] * lM[b])) * ppN[3 * a + b];
+        // c's own factor split by state: e[q][s] = M3[q][s] l_s
+        double e[3][3];
+#pragma unroll
+        for (int s = 0; s < 3; s++) {
+          const double ls = s_lk[P[gidx[s] * np + jc]];
+#pragma unroll
+          for (int q = 0; q < 3; q++) e[q][s] = s_m3[q * 3 + s] * ls;
+        }
+        double num = 0.0, den = 0.0, bj = 0.0, bw = 0.0;
+        int bk = -1, bfa = -1, bmo = -1;
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+          const int md = d_mend3(k);
+          double nm[3], me[3];
+#pragma unroll
+          for (int q = 0; q < 3; q++) {
+            nm[q] = 0.0; me[q] = 0.0;
+#pragma unroll
+            for (int s = 0; s < 3; s++) {
+              if ((md >> s) & 1) me[q] += e[q][s];
+              else nm[q] += e[q][s];
+            }
+          }
+          const double fn = d_one_kid_dn(k, nm[0], nm[1], nm[2]), fm = d_one_kid_dn(k, me[0], me[1], me[2]);
+          const double Jn = w[k] * fn;
+          num += Jn;
+          den += w[k] * (fn + fm);   // (term by term >= Jn: num <= den, pp <= 1)
+          const int fs = sw ? k % 3 : k / 3, ms = sw ? k / 3 : k % 3;
+          if (Jn > bj || (Jn == bj && bk >= 0 && (fs < bfa || (fs == bfa && ms < bmo)))) { bj = Jn; bw = w[k]; bk = k; bfa = fs; bmo = ms; }
+        }
+        int bs = -1;
+        if (bk >= 0) {   // the largest single-state term of the best pair
+          const int md = d_mend3(bk);
+          double bv = 0.0;
+#pragma unroll
+          for (int s = 0; s < 3; s++) {
+            if ((md >> s) & 1) continue;
+            const double v = bw * d_one_kid_dn(bk, e[0][s], e[1][s], e[2][s]);
+            if (v > bv) { bv = v; bs = s; }
+          }
+        }
+        pm_person_dn o;
+        o.person = p0 + jc; o.pad = 0;
+        o.fa_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bfa)); o.mo_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bmo));
+        o.kid_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bs));
+        o.pp = den > 0.0 ? num / den : 0.0;
+        line[p0 + jc] = o;
+      }
+      // ---- peeled families: clamped peels
+      if (W.n_es > 0) {   // (block-uniform)
+        for (int it = threadIdx.x; it < W.n_es * 9; it += T) {   // stage A
+          const int ci = it / 9, k = it % 9;
+          const int2 kd = W.kids[W.n_nuc + ci];
+          const int p0 = A.fam_start[kd.x], jc = kd.y, fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
+          const int nonm = 7 & ~d_mend3(k);
+          double J = 0.0;
+          if (nonm)
+            J = d_es_lk3_vdn<true>(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tba, ws, T, fa, 1 << (k / 3), mo, 1 << (k % 3), jc, nonm);
+          jb[it] = J;
+        }
+        __syncthreads();
+        double* jb2 = jb + (size_t)W.n_es * 9;
+        for (int it = threadIdx.x; it < W.n_es * 4; it += T) {   // stage B
+          const int ci = it / 4, slot = it % 4;
+          const int2 kd = W.kids[W.n_nuc + ci];
+          const int p0 = A.fam_start[kd.x], jc = kd.y, fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
+          double v = -1.0;
+          if (slot == 3) v = d_es_lk3_vdn(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tba, ws, T);
+          else {
+            double bj = 0.0;
+            int bi = -1;
+            for (int q = 0; q < 9; q++) { const double J = jb[ci * 9 + q]; if (J > bj) { bj = J; bi = q; } }
+            if (bi >= 0 && !((d_mend3(bi) >> slot) & 1))
+              v = d_es_lk3_vdn<true>(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tba, ws, T, fa, 1 << (bi / 3), mo, 1 << (bi % 3), jc, 1 << slot);
+          }
+          jb2[it] = v;
+        }
+        __syncthreads();
+        for (int ci = threadIdx.x; ci < W.n_es; ci += T) {   // stage C
+          const int2 kd = W.kids[W.n_nuc + ci];
+          const int p = A.fam_start[kd.x] + kd.y;
+          double num = 0.0, bj = 0.0;
+          int bi = -1;
+          for (int q = 0; q < 9; q++) { const double J = jb[ci * 9 + q]; num += J; if (J > bj) { bj = J; bi = q; } }
+          const double L = jb2[ci * 4 + 3];
+          double bv = 0.0;
+          int bs = -1;
+          for (int s = 0; s < 3; s++) { const double v = jb2[ci * 4 + s]; if (v > bv) { bv = v; bs = s; } }
+          pm_person_dn o;
+          o.person = p; o.pad = 0;
+          o.fa_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bi / 3)); o.mo_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bi % 3));
+          o.kid_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bs));
+          o.pp = L > 0.0 ? fmin(num / L, 1.0) : 0.0;   // (L_f and the terms come from separate peels: rounding may pass 1)
+          line[p] = o;
+        }
+      }
+      __syncthreads();   // the row's entries are visible to the block: the ranking reads what other threads wrote
+      double prev_pp = 0.0;
+      int prev_p = -1;
+      for (int k = 0; k < W.car_k; k++) {
+        double bl = 0.0;
+        int bf = INT_MAX;
+        for (int i = threadIdx.x; i < nk; i += T) {
+          const int2 kd = W.kids[i];
+          const int p = A.fam_start[kd.x] + kd.y;
+          const double d = line[p].pp;
+          const bool after = k == 0 ? d == d : (d < prev_pp || (d == prev_pp && p > prev_p));
+          if (after && fam_lr_before(d, p, bl, bf)) { bl = d; bf = p; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const double ol = __shfl_xor(bl, o, 64);
+          const int of = __shfl_xor(bf, o, 64);
+          if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
+        }
+        if (lane == 0) { s_red[par][wv] = bl; s_redf[par][wv] = bf; }
+        __syncthreads();
+        bl = s_red[par][0]; bf = s_redf[par][0];
+#pragma unroll
+        for (int w = 1; w < NW; w++)
+          if (fam_lr_before(s_red[par][w], s_redf[par][w], bl, bf)) { bl = s_red[par][w]; bf = s_redf[par][w]; }
+        par ^= 1;
+        if (threadIdx.x == 0) {
+          pm_person_dn o;
+          o.person = -1; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
+          if (bf != INT_MAX) o = line[bf];
+          W.car_top[(size_t)row * W.car_k + k] = o;
+        }
+        if (bf == INT_MAX) { prev_pp = -INFINITY; prev_p = INT_MAX; }   // exhausted: every later round is empty too
+        else { prev_pp = bl; prev_p = bf; }
+      }
+    }
+  }
 }

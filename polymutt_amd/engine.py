@@ -127,6 +127,10 @@ EXPORTS = {
     "pm_engine_set_denovo_carriers": (i32, [C.c_void_p, i32, i32]),
     "pm_engine_denovo_carriers": (i32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_engine_set_vcf_denovo": (i32, [C.c_void_p, i32]),
+    "pm_engine_set_vcf_denovo_detail": (i32, [C.c_void_p, i32, i32, i32]),
+    "pm_engine_vcf_denovo_rows": (i32, [C.c_void_p, P(i32), C.c_void_p]),
+    "pm_engine_vcf_denovo_families": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pm_engine_vcf_denovo_carriers": (i32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_host_alloc": (i32, [u64, P(C.c_void_p)]),
     "pm_host_free": (i32, [C.c_void_p]),
     "pm_engine_to_planar": (i32, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
@@ -268,6 +272,7 @@ class Engine:
         self.n_fam = ped_struct.n_fam
         self._fam_k, self._fam_all = 0, False
         self._pdn_k, self._pdn_all = 0, False
+        self._vw_fam_k, self._vw_car_k, self._vw_all = 0, 0, False
 
     def begin_section(self, chrom=PM_CHR_AUTO):
         self._check(self.lib.pm_engine_begin_section(self.h, chrom))
@@ -418,6 +423,50 @@ class Engine:
         three-genotype de novo model in varllk[2] (maximiser varfreq[2], evaluations evals[2]) and DQ = N - varllk[1] in
         denovo_lr; off (the default) leaves every output byte as it was."""
         self._check(self.lib.pm_engine_set_vcf_denovo(self.h, 1 if on else 0))
+        if not on:   # (the engine switches the detail off with it)
+            self._vw_fam_k = self._vw_car_k = 0
+            self._vw_all = False
+
+    def set_vcf_denovo_detail(self, fam_k, car_k, want_all=False):
+        """pm_engine_set_vcf_denovo_detail (after set_vcf_denovo(True)): per row -- a called autosomal site whose DQ is at
+        or above denovo_min_llr -- keep the fam_k families ranked by their term D_f of DQ and the car_k non-founders ranked
+        by their posterior probability of carrying a de novo mutation (each 0 = off or 1..8), and with want_all the whole
+        [rows, n_fam] and [rows, n_person] matrices.  Both 0 switches the feature off."""
+        self._check(self.lib.pm_engine_set_vcf_denovo_detail(self.h, int(fam_k), int(car_k), 1 if want_all else 0))
+        self._vw_fam_k, self._vw_car_k = int(fam_k), int(car_k)
+        self._vw_all = bool(want_all) and (fam_k > 0 or car_k > 0)
+
+    def vcf_denovo_rows(self):
+        """pm_engine_vcf_denovo_rows: the batch indices of the last finished batch's rows, ascending (int32)."""
+        n = i32(0)
+        self._check(self.lib.pm_engine_vcf_denovo_rows(self.h, C.byref(n), None))
+        site = np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            self._check(self.lib.pm_engine_vcf_denovo_rows(self.h, C.byref(n), _ptr(site)))
+        return site
+
+    def vcf_denovo_families(self):
+        """pm_engine_vcf_denovo_families for the last finished batch: (top[rows, fam_k] of FAM_LR_DTYPE, sum[rows],
+        all[rows, n_fam] or None), rows as in vcf_denovo_rows()."""
+        if self._vw_fam_k <= 0:
+            raise RuntimeError("vcf_denovo_families: the feature is off (set_vcf_denovo_detail fam_k)")
+        rows = len(self.vcf_denovo_rows())
+        top = np.zeros((rows, self._vw_fam_k), dtype=FAM_LR_DTYPE)
+        tot = np.zeros(rows, dtype=np.float64)
+        full = np.zeros((rows, self.n_fam), dtype=np.float64) if self._vw_all else None
+        self._check(self.lib.pm_engine_vcf_denovo_families(self.h, _ptr(top), _ptr(tot), None if full is None else _ptr(full)))
+        return top, tot, full
+
+    def vcf_denovo_carriers(self):
+        """pm_engine_vcf_denovo_carriers for the last finished batch: (top[rows, car_k], all[rows, n_person] or None) of
+        PERSON_DN_DTYPE (genotypes as GLF indices 0..9), rows as in vcf_denovo_rows()."""
+        if self._vw_car_k <= 0:
+            raise RuntimeError("vcf_denovo_carriers: the feature is off (set_vcf_denovo_detail car_k)")
+        rows = len(self.vcf_denovo_rows())
+        top = np.zeros((rows, self._vw_car_k), dtype=PERSON_DN_DTYPE)
+        full = np.zeros((rows, self.n_person), dtype=PERSON_DN_DTYPE) if self._vw_all else None
+        self._check(self.lib.pm_engine_vcf_denovo_carriers(self.h, _ptr(top), None if full is None else _ptr(full)))
+        return top, full
 
     def stuck_site(self):
         """pm_engine_stuck_site: the first site of the last finished batch whose Brent hit ITMAX (-1: none)."""

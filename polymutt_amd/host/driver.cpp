@@ -49,7 +49,8 @@ Options parse_command_line(int argc, char** argv) {
       {"gpu", 'i', &o.device}, {"batch", 'i', &o.batch}, {"io_threads", 'i', &o.io_threads}, {"engines", 'i', &o.engines},
       {"in_blocks", 's', &o.blocksIn}, {"glf2blocks", 's', &o.blocksOut}, {"block_sites", 'i', &o.blockSites}, {"exact_log10", 'b', &o.exact_log10}, {"numerics", 's', &o.numerics},
       {"denovo_families", 'i', &o.denovo_families}, {"denovo_carriers", 'i', &o.denovo_carriers},
-      {"vcf_denovo", 'b', &o.vcf_denovo},
+      {"vcf_denovo", 'b', &o.vcf_denovo}, {"vcf_denovo_families", 'i', &o.vcf_denovo_families},
+      {"vcf_denovo_carriers", 'i', &o.vcf_denovo_carriers},
   };
   auto assign = [](Flag& f, const char* v) {
     switch (f.kind) {
@@ -71,6 +72,8 @@ Options parse_command_line(int argc, char** argv) {
         found = true;
         if (f.ptr == &o.denovo_families) o.denovo_families_given = true;
         if (f.ptr == &o.denovo_carriers) o.denovo_carriers_given = true;
+        if (f.ptr == &o.vcf_denovo_families) o.vcf_denovo_families_given = true;
+        if (f.ptr == &o.vcf_denovo_carriers) o.vcf_denovo_carriers_given = true;
         if (f.kind == 'b') { *(bool*)f.ptr = true; break; }
         if (!hasEq) {
           if (a + 1 >= argc) throw FatalError(std::string("Missing value for option --") + name + "\n");
@@ -100,6 +103,14 @@ Options parse_command_line(int argc, char** argv) {
     if (o.denovo_families < 1 || o.denovo_families > 8) throw FatalError("--denovo_families takes a family count from 1 to 8\n");
   }
   if (o.vcf_denovo && o.vcfInFile.empty()) throw FatalError("--vcf_denovo needs --in_vcf\n");
+  if (o.vcf_denovo_families_given) {
+    if (!o.vcf_denovo) throw FatalError("--vcf_denovo_families needs --vcf_denovo\n");
+    if (o.vcf_denovo_families < 1 || o.vcf_denovo_families > 8) throw FatalError("--vcf_denovo_families takes a family count from 1 to 8\n");
+  }
+  if (o.vcf_denovo_carriers_given) {
+    if (!o.vcf_denovo) throw FatalError("--vcf_denovo_carriers needs --vcf_denovo\n");
+    if (o.vcf_denovo_carriers < 1 || o.vcf_denovo_carriers > 8) throw FatalError("--vcf_denovo_carriers takes a person count from 1 to 8\n");
+  }
   if (o.denovo_carriers_given) {
     if (!o.denovo) throw FatalError("--denovo_carriers needs --denovo\n");
     if (!o.vcfInFile.empty()) throw FatalError("--denovo_carriers is not available with --in_vcf\n");

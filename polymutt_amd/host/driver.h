@@ -35,6 +35,11 @@ struct Options {
   // --vcf_denovo (with --in_vcf): biallelic autosomal SNV records whose three-genotype de novo model beats the standard
   // one by DQ >= --minLLR_denovo get ;DQ= after DP= (pm_engine_set_vcf_denovo; --rate_denovo, --tstv_denovo apply)
   bool vcf_denovo = false;
+  // --vcf_denovo_families K / --vcf_denovo_carriers K (each with --vcf_denovo, K in 1..8): a record that gets ;DQ= also names
+  // the K families with the largest share of DQ (DNF / DNFLR) and the K non-founders most likely to carry a de novo
+  // mutation (DNC / DNCP / DNCE), in the formats of --denovo_families / --denovo_carriers (pm_engine_set_vcf_denovo_detail)
+  int vcf_denovo_families = 0, vcf_denovo_carriers = 0;
+  bool vcf_denovo_families_given = false, vcf_denovo_carriers_given = false;
   std::string cmd;
   pm_params params() const;
 };
@@ -88,6 +93,20 @@ class SiteEvaluator {
   virtual void denovo_carriers(pm_person_dn* top) { (void)top; throw FatalError("--denovo_carriers needs the GPU engine\n"); }
   // --vcf_denovo: once, before the first batch; the results then carry DQ in denovo_lr (pm_engine_set_vcf_denovo)
   virtual void set_vcf_denovo(bool on) { (void)on; throw FatalError("--vcf_denovo is not supported by this evaluator\n"); }
+  // --vcf_denovo_families / --vcf_denovo_carriers: set_vcf_denovo_detail once, after set_vcf_denovo(true) and before the
+  // first batch; then, for the batch the last run_vcf() returned (also after it threw a BrentError: the rows before the
+  // stuck site), vcf_denovo_rows returns the row count and writes the rows' batch indices to site (may be null), and the
+  // two readers hand out the rows [rows][K] (pm_engine_vcf_denovo_rows / _families / _carriers)
+  virtual void set_vcf_denovo_detail(int fam_k, int car_k) {
+    (void)fam_k; (void)car_k;
+    throw FatalError("--vcf_denovo_families / --vcf_denovo_carriers is not supported by this evaluator\n");
+  }
+  virtual int vcf_denovo_rows(int32_t* site) {
+    (void)site;
+    throw FatalError("--vcf_denovo_families / --vcf_denovo_carriers is not supported by this evaluator\n");
+  }
+  virtual void vcf_denovo_families(pm_fam_lr* top) { (void)top; throw FatalError("--vcf_denovo_families is not supported by this evaluator\n"); }
+  virtual void vcf_denovo_carriers(pm_person_dn* top) { (void)top; throw FatalError("--vcf_denovo_carriers is not supported by this evaluator\n"); }
   // Host memory for the batch buffers (the engine: page-locked, for asynchronous copies)
   virtual void* host_alloc(size_t bytes);
   virtual void host_free(void* p);

@@ -63,6 +63,7 @@ class EngineEvaluator : public SiteEvaluator {
                int* n_rows) override {
     (void)n_person;
     check(pm_engine_set_posterior_carry(eng_[0], seen_ ? 1 : 0));
+    last_ = eng_[0];
     int rc = pm_engine_run_vcf(eng_[0], n, pl, ref, res, calls, n_rows);
     if (rc == PM_EBRENT) throw stuck(eng_[0], *n_rows);
     check(rc);
@@ -117,6 +118,23 @@ class EngineEvaluator : public SiteEvaluator {
   }
   void set_vcf_denovo(bool on) override {
     for (auto* e : eng_) check(pm_engine_set_vcf_denovo(e, on ? 1 : 0));
+  }
+  void set_vcf_denovo_detail(int fam_k, int car_k) override {
+    for (auto* e : eng_) check(pm_engine_set_vcf_denovo_detail(e, fam_k, car_k, 0));
+  }
+  int vcf_denovo_rows(int32_t* site) override {   // (the engine that ran the batch last returned)
+    if (!last_) throw FatalError("GPU engine error: no finished batch\n");
+    int32_t n = 0;
+    check(pm_engine_vcf_denovo_rows(last_, &n, site));
+    return n;
+  }
+  void vcf_denovo_families(pm_fam_lr* top) override {
+    if (!last_) throw FatalError("GPU engine error: no finished batch\n");
+    check(pm_engine_vcf_denovo_families(last_, top, nullptr, nullptr));
+  }
+  void vcf_denovo_carriers(pm_person_dn* top) override {
+    if (!last_) throw FatalError("GPU engine error: no finished batch\n");
+    check(pm_engine_vcf_denovo_carriers(last_, top, nullptr));
   }
   void* host_alloc(size_t bytes) override {
     void* p = nullptr;

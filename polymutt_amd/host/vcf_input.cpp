@@ -344,6 +344,15 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       fprintf(out, "%s",
               "##INFO=<ID=DQ,Number=1,Type=Float,Description=\"De Novo Mutation Quality: log10 likelihood ratio of the de novo "
               "mutation model and the standard model\">\n");
+    if (opt.vcf_denovo && opt.vcf_denovo_families > 0)   // (the Descriptions of --denovo_families / --denovo_carriers, vcf.cpp)
+      fprintf(out, "%s",
+              "##INFO=<ID=DNF,Number=.,Type=String,Description=\"Families With the Largest Shares of DQ, Largest First\">\n"
+              "##INFO=<ID=DNFLR,Number=.,Type=Float,Description=\"Share of DQ (log10 Likelihood Ratio) of Each DNF Family\">\n");
+    if (opt.vcf_denovo && opt.vcf_denovo_carriers > 0)
+      fprintf(out, "%s",
+              "##INFO=<ID=DNC,Number=.,Type=String,Description=\"Persons Most Likely to Carry a De Novo Mutation, Most Likely First\">\n"
+              "##INFO=<ID=DNCP,Number=.,Type=Float,Description=\"Posterior Probability of a De Novo Mutation in Each DNC Person\">\n"
+              "##INFO=<ID=DNCE,Number=.,Type=String,Description=\"Most Likely Event of Each DNC Person, FatherxMother>Child Genotypes\">\n");
     fprintf(out, "%s",
             "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
             "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype Quality\">\n"
@@ -365,6 +374,8 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   const double tstv = 2.0, prior_ts = tstv / (tstv + 1), prior_tv = 0.5 / (tstv + 1);
 
   if (opt.vcf_denovo) eval.set_vcf_denovo(true);
+  const int dnf_k = opt.vcf_denovo ? opt.vcf_denovo_families : 0, dnc_k = opt.vcf_denovo ? opt.vcf_denovo_carriers : 0;
+  if (dnf_k > 0 || dnc_k > 0) eval.set_vcf_denovo_detail(dnf_k, dnc_k);
   const int B = std::max(1, opt.batch);
   // Two batches: the main thread reads, classifies and parses records into one while the flusher thread runs the
   // engine on the other, formats its records and hands their text to the writer thread.  A batch's PL rows are in
@@ -413,7 +424,15 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   // The state a record is printed with: its own (a computed record) or the previous computed record's (a record
   // without data, PedVCF.cpp:113-122): QUAL, the AF minimiser and every person's call.
   // dq (--vcf_denovo): the record's own DQ tag; never carried to a record without data
-  struct RecState { double qual, min; const pm_vcf_call* calls; bool has_dq = false; double dq = 0.0; };
+  // dnf / dnc (--vcf_denovo_families / --vcf_denovo_carriers): the ranked families and non-founders of a record with DQ
+  struct RecState {
+    double qual, min;
+    const pm_vcf_call* calls;
+    bool has_dq = false;
+    double dq = 0.0;
+    const pm_fam_lr* dnf = nullptr;
+    const pm_person_dn* dnc = nullptr;
+  };
   auto fresh_state = [&](const Pending& r, const pm_site_result* Rs, const pm_vcf_call* C) {
     // mono/poly -> QUAL (PedVCF.cpp:136-152), with the reference's operator-precedence slip
     const double mono = Rs->varllk[0], poly = Rs->varllk[1];
@@ -491,8 +510,36 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     if (hn >= (int)sizeof(head)) { putf(hn); w += snprintf(w, (size_t)hn + 1, "\t%.2f\t", S.qual); } else putf(hn);
     fld(6);
     const char* fmt_s = fs.PL_idx > 0 ? "GT:GQ:DP:PL" : "GT:GQ:DP:GL";
-    char dq_s[64] = "";
-    if (S.has_dq) snprintf(dq_s, sizeof(dq_s), ";DQ=%.3f", S.dq);
+    std::string dq_t;
+    if (S.has_dq) {
+      char v[64];
+      snprintf(v, sizeof(v), ";DQ=%.3f", S.dq);
+      dq_t = v;
+      if (S.dnf) {   // ;DNF=<famid>[,...];DNFLR=<%.3f>[,...] as vcf.cpp prints them (padding entries are not printed)
+        std::string ids, lrs;
+        for (int k = 0; k < dnf_k && S.dnf[k].fam >= 0 && S.dnf[k].fam < (int)ped.families.size(); k++) {
+          snprintf(v, sizeof(v), "%.3f", S.dnf[k].lr);
+          if (k) { ids += ','; lrs += ','; }
+          ids += ped.families[S.dnf[k].fam].famid;
+          lrs += v;
+        }
+        if (!ids.empty()) { dq_t += ";DNF="; dq_t += ids; dq_t += ";DNFLR="; dq_t += lrs; }
+      }
+      if (S.dnc) {   // ;DNC=<pid>[,...];DNCP=<%.4g>[,...];DNCE=<fa>x<mo>><kid>[,...]
+        static const char* g2[10] = {"AA", "AC", "AG", "AT", "CC", "CG", "CT", "GG", "GT", "TT"};
+        auto gs = [&](int g) { return (g >= 0 && g < 10) ? g2[g] : ".."; };
+        std::string ids, pps, evs;
+        for (int k = 0; k < dnc_k && S.dnc[k].person >= 0 && S.dnc[k].person < np; k++) {
+          snprintf(v, sizeof(v), "%.4g", S.dnc[k].pp);
+          if (k) { ids += ','; pps += ','; evs += ','; }
+          ids += ped.column_pid[S.dnc[k].person];
+          pps += v;
+          evs += gs(S.dnc[k].fa_g); evs += 'x'; evs += gs(S.dnc[k].mo_g); evs += '>'; evs += gs(S.dnc[k].kid_g);
+        }
+        if (!ids.empty()) { dq_t += ";DNC="; dq_t += ids; dq_t += ";DNCP="; dq_t += pps; dq_t += ";DNCE="; dq_t += evs; }
+      }
+    }
+    const char* dq_s = dq_t.c_str();
     hn = snprintf(head, sizeof(head), "\tAF=%.2f;AC=%d;DP=%d%s\t%s", 1 - S.min, AC, totalDepth, dq_s, fmt_s);
     if (hn >= (int)sizeof(head)) { putf(hn); w += snprintf(w, (size_t)hn + 1, "\tAF=%.2f;AC=%d;DP=%d%s\t%s", 1 - S.min, AC, totalDepth, dq_s, fmt_s); }
     else putf(hn);
@@ -581,6 +628,20 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
           if (pend[k]->computed && pend[k]->slot >= e.valid) { npend = k; break; }
       }
     }
+    // the batch's rows (the sites with DQ at or above the threshold; after a stuck Brent those before it): slot -> row
+    std::vector<int32_t> row_of;
+    std::vector<pm_fam_lr> dnf;
+    std::vector<pm_person_dn> dnc;
+    if (bb.nb > 0 && (dnf_k > 0 || dnc_k > 0)) {
+      const int nr = eval.vcf_denovo_rows(nullptr);
+      std::vector<int32_t> site((size_t)std::max(1, nr));
+      if (nr > 0) eval.vcf_denovo_rows(site.data());
+      row_of.assign((size_t)bb.nb, -1);
+      for (int k = 0; k < nr; k++)
+        if (site[k] >= 0 && site[k] < bb.nb) row_of[site[k]] = k;
+      if (dnf_k > 0) { dnf.resize((size_t)std::max(1, nr) * dnf_k); eval.vcf_denovo_families(dnf.data()); }
+      if (dnc_k > 0) { dnc.resize((size_t)std::max(1, nr) * dnc_k); eval.vcf_denovo_carriers(dnc.data()); }
+    }
     double t1 = now();
     tm[3] += t1 - t0;
     // the state each record prints with (sequential: a record without data takes the last computed one's)
@@ -588,8 +649,12 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     RecState cur{st.qual, st.min, st.calls.data()};
     for (size_t k = 0; k < npend; k++) {
       const Pending& r = *pend[k];
-      if (r.computed) cur = fresh_state(r, &bb.res[r.slot], calls + (size_t)bb.res[r.slot].call_row * np);
-      else cur.has_dq = false;
+      if (r.computed) {
+        cur = fresh_state(r, &bb.res[r.slot], calls + (size_t)bb.res[r.slot].call_row * np);
+        const int row = (cur.has_dq && !row_of.empty()) ? row_of[r.slot] : -1;
+        if (row >= 0 && dnf_k > 0) cur.dnf = dnf.data() + (size_t)row * dnf_k;
+        if (row >= 0 && dnc_k > 0) cur.dnc = dnc.data() + (size_t)row * dnc_k;
+      } else { cur.has_dq = false; cur.dnf = nullptr; cur.dnc = nullptr; }
       states[k] = cur;
     }
     std::vector<std::string>& T = texts[tcur];
