@@ -10,6 +10,44 @@
 #pragma once
 #include "log_table.h"
 
+// PM_SERIAL_V0 (compile-time, -DPM_SERIAL_V0=1; the hipRTC kernels get it through their compile options) restores the
+// serial path of an objective evaluation as it was before it was shortened -- the argument re-loads, the identity
+// operands of the masked DPP steps, the readfirstlane branch tests, the table entry by scalar load in every flavour --
+// for the A/B and the byte-equality test (lib_exp/serial_v0.so, polymutt_amd/Makefile).  Both paths run the same FP64
+// operations in the same order on every value that reaches a result.  A later clean-up removes the switch.
+#ifdef PM_SERIAL_V0
+#define PM_SERIAL_NEW 0
+#else
+#define PM_SERIAL_NEW 1
+#endif
+
+// PM_ISA_MARK (tools/isa_mix.py): assembler comments that delimit the regions whose instruction mix the tool reports
+#ifdef PM_ISA_MARK
+#define PM_MARK(name) asm volatile("; PM_MARK " name)
+#else
+#define PM_MARK(name) ((void)0)
+#endif
+
+// A WAVE-UNIFORM value pinned in scalar registers at this point (loaded once; the compiler otherwise rematerialises a
+// kernel argument's load, with its lgkmcnt(0) wait, inside the Brent loop).  Not for per-lane values.
+template <typename V>
+__device__ __forceinline__ V pm_pin_s(V v) {
+#if PM_SERIAL_NEW
+  asm volatile("" : "+s"(v));
+#endif
+  return v;
+}
+
+// A wave-uniform predicate as a branch condition: the compare's lane mask tested as a whole (one v_cmp and a scalar
+// branch on it) instead of a select, a readfirstlane and a bit test
+__device__ __forceinline__ bool pm_uniform(bool p) {
+#if PM_SERIAL_NEW
+  return __builtin_amdgcn_ballot_w64(p) != 0;
+#else
+  return __builtin_amdgcn_readfirstlane((int)p) != 0;
+#endif
+}
+
 #ifndef PM_LOG10_2_HI
 #define PM_LOG10_2_HI 0x1.3441350800000p-2
 #define PM_LOG10_2_LO 0x1.f79fef311f12bp-34
@@ -31,21 +69,29 @@ __device__ __forceinline__ double pos_div(double n, double d) {
 }
 
 // One step of the wave product reduction on the DPP crossbar (VALU latency, no LDS round trip): multiply
-// by the (mantissa, exponent) of the lane selected by CTRL; rows outside ROWMASK keep their value (the
-// DPP `old` operand is the identity 1.0 x 2^0).
+// by the (mantissa, exponent) of the lane selected by CTRL.  Rows outside ROWMASK are never read afterwards (wave_prod
+// reads lane 63, wave_prod_pair lanes 31 and 63, both in rows that every masked step writes, and a DPP source is read
+// before the write), so they need no identity 1.0 x 2^0 as the DPP `old` operand: it is the previous step's partner
+// (plo, phi: a dead register, so neither a constant nor a copy is materialised; those rows multiply by a factor in
+// (0, 1) once more and stay far above underflow).  PM_SERIAL_V0 keeps the identity and its two v_mov per masked step.
 template <int CTRL, int ROWMASK>
-__device__ __forceinline__ void dpp_prod_step(double& m, int& e) {
+__device__ __forceinline__ void dpp_prod_step(double& m, int& e, int& plo, int& phi) {
   const int lo = __double2loint(m), hi = __double2hiint(m);
   int olo, ohi, oe;
-  if constexpr (ROWMASK == 0xF) {   // every row written: no identity `old` operand (saves its two v_mov per step)
+  if constexpr (ROWMASK == 0xF) {   // every row written: no `old` operand
     olo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, false);
     ohi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, false);
     oe = __builtin_amdgcn_update_dpp(0, e, CTRL, ROWMASK, 0xF, false);   // (folds into one v_add_u32_dpp)
+  } else if constexpr (PM_SERIAL_NEW) {
+    olo = __builtin_amdgcn_update_dpp(plo, lo, CTRL, ROWMASK, 0xF, false);
+    ohi = __builtin_amdgcn_update_dpp(phi, hi, CTRL, ROWMASK, 0xF, false);
+    oe = __builtin_amdgcn_update_dpp(0, e, CTRL, ROWMASK, 0xF, false);
   } else {
     olo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROWMASK, 0xF, false);
     ohi = __builtin_amdgcn_update_dpp(0x3FF00000, hi, CTRL, ROWMASK, 0xF, false);
     oe = __builtin_amdgcn_update_dpp(0, e, CTRL, ROWMASK, 0xF, false);
   }
+  plo = olo; phi = ohi;
   m = m * __hiloint2double(ohi, olo);   // no renormalisation: 64 factors in [1/16, 1) stay >= 2^-256
   e += oe;
 }
@@ -54,12 +100,13 @@ __device__ __forceinline__ void dpp_prod_step(double& m, int& e) {
 // (every lane of a row of 16 then holds the row product), row_bcast15 / row_bcast31 (lane 63 ends with
 // ((R3 R2)(R1 R0))), broadcast from lane 63.  Deterministic for any batch, identical in every lane.
 __device__ __forceinline__ void wave_prod(double& m, int& e) {
-  dpp_prod_step<0xB1, 0xF>(m, e);    // quad_perm [1,0,3,2]
-  dpp_prod_step<0x4E, 0xF>(m, e);    // quad_perm [2,3,0,1]
-  dpp_prod_step<0x141, 0xF>(m, e);   // row_half_mirror
-  dpp_prod_step<0x140, 0xF>(m, e);   // row_mirror
-  dpp_prod_step<0x142, 0xA>(m, e);   // row_bcast:15 -> rows 1, 3
-  dpp_prod_step<0x143, 0xC>(m, e);   // row_bcast:31 -> rows 2, 3
+  int plo = 0, phi = 0;
+  dpp_prod_step<0xB1, 0xF>(m, e, plo, phi);    // quad_perm [1,0,3,2]
+  dpp_prod_step<0x4E, 0xF>(m, e, plo, phi);    // quad_perm [2,3,0,1]
+  dpp_prod_step<0x141, 0xF>(m, e, plo, phi);   // row_half_mirror
+  dpp_prod_step<0x140, 0xF>(m, e, plo, phi);   // row_mirror
+  dpp_prod_step<0x142, 0xA>(m, e, plo, phi);   // row_bcast:15 -> rows 1, 3
+  dpp_prod_step<0x143, 0xC>(m, e, plo, phi);   // row_bcast:31 -> rows 2, 3
   const int lo = __builtin_amdgcn_readlane(__double2loint(m), 63), hi = __builtin_amdgcn_readlane(__double2hiint(m), 63);
   int ev;
   m = frexp(__hiloint2double(hi, lo), &ev);   // one normalisation (exact: the mantissa bits are those of the
@@ -70,11 +117,12 @@ __device__ __forceinline__ void wave_prod(double& m, int& e) {
 // end in lane 31, rows 2+3 in lane 63), then each half takes its own lane's product -- the order of wave_prod's first
 // five steps.  Every lane of a half ends with that half's (m, e), m normalised.
 __device__ __forceinline__ void wave_prod_pair(double& m, int& e) {
-  dpp_prod_step<0xB1, 0xF>(m, e);    // quad_perm [1,0,3,2]
-  dpp_prod_step<0x4E, 0xF>(m, e);    // quad_perm [2,3,0,1]
-  dpp_prod_step<0x141, 0xF>(m, e);   // row_half_mirror
-  dpp_prod_step<0x140, 0xF>(m, e);   // row_mirror
-  dpp_prod_step<0x142, 0xA>(m, e);   // row_bcast:15 -> rows 1, 3
+  int plo = 0, phi = 0;
+  dpp_prod_step<0xB1, 0xF>(m, e, plo, phi);    // quad_perm [1,0,3,2]
+  dpp_prod_step<0x4E, 0xF>(m, e, plo, phi);    // quad_perm [2,3,0,1]
+  dpp_prod_step<0x141, 0xF>(m, e, plo, phi);   // row_half_mirror
+  dpp_prod_step<0x140, 0xF>(m, e, plo, phi);   // row_mirror
+  dpp_prod_step<0x142, 0xA>(m, e, plo, phi);   // row_bcast:15 -> rows 1, 3
   const double mA = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(m), 31), __builtin_amdgcn_readlane(__double2loint(m), 31));
   const double mB = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(m), 63), __builtin_amdgcn_readlane(__double2loint(m), 63));
   const int eA = __builtin_amdgcn_readlane(e, 31), eB = __builtin_amdgcn_readlane(e, 63);
@@ -101,6 +149,25 @@ __device__ __forceinline__ double log10_mant_u(double m, int e) {
   p = fma(z, p, PM_LOG10_SER_1);
   const double de = (double)e;
   return fma(z, p, L) + (de * PM_LOG10_2_HI + de * PM_LOG10_2_LO);
+}
+
+// log10_mant_u with the table entry from a 2 KB LDS copy of c_log10_tab (tab: 256 doubles, 16-byte aligned, filled at
+// kernel start): the index is wave-uniform, so one broadcast ds_read_b128 returns the same two doubles as the scalar load
+// from constant memory -- the same operations on the same values, another path for the one load the evaluation's
+// serial path has to wait for.  (The precompiled k_brent only, chosen per flavour: PM_LOG10_LDS in engine_dev.h.)
+struct __attribute__((aligned(16))) PmLogEntry { double c, L; };
+__device__ __forceinline__ double log10_mant_u_lds(double m, int e, const double* tab) {
+  if (m == 0.0) return -__builtin_inf();
+  const int i = (__builtin_amdgcn_readfirstlane(__double2hiint(m)) >> 13) & 0x7F;
+  const PmLogEntry t = ((const PmLogEntry*)tab)[i];
+  const double z = fma(m, t.c, -1.0);
+  double p = fma(z, PM_LOG10_SER_6, PM_LOG10_SER_5);
+  p = fma(z, p, PM_LOG10_SER_4);
+  p = fma(z, p, PM_LOG10_SER_3);
+  p = fma(z, p, PM_LOG10_SER_2);
+  p = fma(z, p, PM_LOG10_SER_1);
+  const double de = (double)e;
+  return fma(z, p, t.L) + (de * PM_LOG10_2_HI + de * PM_LOG10_2_LO);
 }
 
 // log10_mant_u for a mantissa uniform over each half-wave (wave_prod_pair): the two halves' table entries by scalar loads
@@ -137,6 +204,9 @@ __device__ __forceinline__ void pm_brent_init(PmBrent& B, double tol, int itmax)
   B.a = 0.0001; B.c = 0.5; B.x = 0.9999;   // Brent starts at b = 0.9999, outside [a, c]
   B.mn = B.fmin = B.w = B.v = B.fw = B.fv = 0.0;
   B.delta = B.d = 0.0;
+#ifdef PM_BRENT_UNIFORM   // (the caller's tol and itmax are wave-uniform -- kernel arguments: loaded once per item)
+  tol = pm_pin_s(tol); itmax = pm_pin_s(itmax);
+#endif
   B.tol = tol;
   B.phase = 1; B.iter = 0; B.nev = 1; B.itmax = itmax;   // nev: f(a) counted
   B.ok = false;

@@ -1270,6 +1270,7 @@ __device__ __forceinline__ void hoist_quad_t(const DevArgs& A, const ItemCtx& I,
     // slot s has landed: only the later slots' DMA (3 instructions each, at most QD_AHEAD - 1 of them) may be outstanding
     vm_wait_slots(QD_AHEAD - 1 < S - 1 - s ? QD_AHEAD - 1 : S - 1 - s);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (DNV) PM_MARK("hoist_dn_slot_begin"); else PM_MARK("hoist_c7_slot_begin");
     const uint32_t* b = rw + (s % QB) * (QSLOT / 4);
     // byte j of a plane dword: person j of the family (0 father, 1 mother, 2 / 3 kids)
     uint32_t w[3];   // planes g11, g12, g22
@@ -1354,6 +1355,7 @@ __device__ __forceinline__ void hoist_quad_t(const DevArgs& A, const ItemCtx& I,
       // slots' table lookups are then live at once (2 KB of spills)
       asm volatile("" : "+v"(a[s][0]), "+v"(a[s][1]), "+v"(a[s][2]), "+v"(a[s][3]), "+v"(m0), "+v"(e0));
     }
+    if constexpr (DNV) PM_MARK("hoist_dn_slot_end"); else PM_MARK("hoist_c7_slot_end");
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -1503,8 +1505,22 @@ __device__ __forceinline__ double log10_mant(double m, int e) {
 #define PM_LOG10_TAB 1   // block_logprod's log10: the table form (0: the atanh series of log10_mant)
 #endif
 
-template <int T>
-__device__ __forceinline__ double block_logprod(double m, int e, double* red, int* rede, int& par) {
+// PM_LOG10_LDS: the k_brent flavours whose table log10 reads its entry from an LDS copy of the table
+// (log10_mant_u_lds) instead of a scalar load from constant memory -- bit 0: QUAD plans (QD), bit 1: the lean kernels
+// on prefetched planes (PF), bit 2: every other flavour.  PM_SERIAL_V0: none.  Measured per flavour:
+// the QUAD headline gains 1 %, the PF kernels lose (plain quads 9 %: the 2 KB come out of the planes' LDS budget) or tie
+// (trios), the others were not measured and keep the scalar load.
+#ifndef PM_LOG10_LDS
+#define PM_LOG10_LDS 1
+#endif
+#ifdef PM_SERIAL_V0
+#undef PM_LOG10_LDS
+#define PM_LOG10_LDS 0
+#endif
+
+// (l10: the LDS copy of c_log10_tab when L10LDS)
+template <int T, bool L10LDS = false>
+__device__ __forceinline__ double block_logprod(double m, int e, double* red, int* rede, int& par, const double* l10 = nullptr) {
   wave_prod(m, e);
   if (T > 64) {
     constexpr int W = T / 64;
@@ -1519,6 +1535,7 @@ __device__ __forceinline__ double block_logprod(double m, int e, double* red, in
     }
     par ^= 1;
   }
+  if constexpr (L10LDS && PM_LOG10_TAB) return log10_mant_u_lds(m, e, l10);
   return PM_LOG10_TAB ? log10_mant_u(m, e) : log10_mant(m, e);
 }
 
@@ -1792,12 +1809,16 @@ k_brent(DevArgs A, int list) {
   constexpr bool EPO = EP && NF == 1;
   constexpr bool PROD = NUM != PM_NUM_EXACT;
   constexpr bool POLYK = NUM == PM_NUM_POLY && !GEN;
+  constexpr bool L10 = ((QD ? 1 : PF ? 2 : 4) & PM_LOG10_LDS) != 0;   // the table log10's entry from LDS (s_l10)
   __shared__ double s_lk[256];
+  __shared__ __attribute__((aligned(16))) double s_l10[L10 ? 256 : 2];
   __shared__ double s_M[(GEN || DN) ? 100 : 1];
   __shared__ double s_red[T > 64 ? 96 : 1];
   __shared__ int s_rede[T > 64 ? 32 : 1];
   __shared__ __attribute__((aligned(16))) int s_u[POLYK && !QD ? S * T : 4];   // packed lane plan (unit_pack, lane-major)
   for (int i = threadIdx.x; i < 256; i += T) s_lk[i] = A.lktab[i];
+  if constexpr (L10)
+    for (int i = threadIdx.x; i < 256; i += T) s_l10[i] = c_log10_tab[i];
   if constexpr (GEN || DN)
     for (int i = threadIdx.x; i < 100; i += T) s_M[i] = A.M[i];
   if constexpr (POLYK && !QD)   // (QUAD plans address families by slot and lane: no lane plan)
@@ -1980,7 +2001,7 @@ k_brent(DevArgs A, int list) {
         if (mdn) {
           double m; int e;
           lane_poly_top<S, NC>((const double(*)[NC])cond, m, e, lm0, le0);
-          mono_dn = block_logprod<T>(m, e, s_red, s_rede, par);
+          mono_dn = block_logprod<T, L10>(m, e, s_red, s_rede, par, s_l10);
         }
         if (threadIdx.x == 0) {
           if (it != it_first) {
@@ -2064,7 +2085,9 @@ k_brent(DevArgs A, int list) {
     const bool single = !A.vcf && ((cfg == 0) || (A.single_nuclear && !A.unrelated));
     // One evaluation site for the objective: the three bracketing evaluations of OptimizeFrequency
     // (:432-444) and every Brent step (core/MathGold.cpp:81-177) run through the same loop body.
-    const double tol = A.precision;
+    // (pinned once per item: the compiler otherwise re-loads both arguments, each behind an lgkmcnt(0) wait, in every evaluation)
+    const double tol = pm_pin_s(A.precision);
+    const int itmax = PM_SERIAL_NEW ? pm_pin_s(A.itmax) : 0;   // (PM_SERIAL_V0 reads A.itmax in the loop, as before)
     double a = 0.0001, b = 0.9999, c = 0.5;
     double mn = 0, fmin = 0, w = 0, v = 0, fw = 0, fv = 0, delta = 0.0, d = 0.0;
     // OptimizeFrequency (NucFamGenotypeLikelihood.cpp:432-441) evaluates fa = f(a), fb = f(b), fc = f(c) and
@@ -2082,13 +2105,13 @@ k_brent(DevArgs A, int list) {
         // de novo monomorphism item) takes the reverse form M = f, t = g / f with masking.
         const double g = 1 - x;
         double m; int e;
-        if (__builtin_amdgcn_readfirstlane((int)(g > 0.0))) {
+        if (pm_uniform(g > 0.0)) {
           // (r from the hardware reciprocal + a Newton step instead of the division: measured no faster)
           lane_poly_r<S, NC>(pos_div(x, g), (g * g) * (g * g), (const double(*)[NC])cond, m, e, lm0, le0);
-          tot = block_logprod<T>(m, e, s_red, s_rede, par);
+          tot = block_logprod<T, L10>(m, e, s_red, s_rede, par, s_l10);
         } else {
           lane_poly_top<S, NC>((const double(*)[NC])cond, m, e, lm0, le0);   // x = 1: L = a0 per family, log10(x^4) = 0
-          tot = block_logprod<T>(m, e, s_red, s_rede, par);
+          tot = block_logprod<T, L10>(m, e, s_red, s_rede, par, s_l10);
         }
       } else if (PROD) {
         double m = 1.0; int e = 0;
@@ -2096,7 +2119,7 @@ k_brent(DevArgs A, int list) {
           if (!(ES && EP && A.ep_only)) lane_prod<S, GEN>(x, unit, (const double(*)[9])cond, fl, pmode, m, e);
         if constexpr (ES && EP && EPE > 0) {   // register-resident coefficients first (independent Horner chains)
           const double g = 1 - x;
-          if (__builtin_amdgcn_readfirstlane((int)(g > 0.0))) {
+          if (pm_uniform(g > 0.0)) {
             // EPR: every family in the one direction L = g^D sum_a c_a t^a, t = f / g (t in [1e-4, 1e4] on Brent's
             // bracket; non-negative terms, no cancellation), by FMA Horner over the PDM + 1 registers (zeros above D
             // leave the sum's bits unchanged); g^D of all the lane's families as one power g^edl (edl <= 32).  The
@@ -2158,7 +2181,7 @@ k_brent(DevArgs A, int list) {
             m = frexp(m * mv, &e2);
             e += e1 + e2;
           }
-        tot = block_logprod<T>(m, e, s_red, s_rede, par);
+        tot = block_logprod<T, L10>(m, e, s_red, s_rede, par, s_l10);
       } else {
         double part = lane_loglik<S, GEN>(x, unit, (const double(*)[9])cond, fl, pmode, A.vcf != 0);
         if (ES && A.ext_count)
@@ -2188,7 +2211,7 @@ k_brent(DevArgs A, int list) {
           else if (fu <= fv || v == mn || v == w) { v = u; fv = fu; }
         }
       }
-      if (++iter > A.itmax) break;   // ITMAX: numerror("ScalarMinimizer::Brent got stuck")
+      if (++iter > (PM_SERIAL_NEW ? itmax : A.itmax)) break;   // ITMAX: numerror("ScalarMinimizer::Brent got stuck")
       const double middle = 0.5 * (a + c);
       const double tol1 = tol * fabs(mn) + 3.0e-10;
       const double tol2 = 2.0 * tol1;

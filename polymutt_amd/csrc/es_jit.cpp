@@ -1747,8 +1747,15 @@ bool compile(const std::string& src, std::vector<char>* code, std::string* err, 
   // -ffp-contract=off: only the explicit fma() of the generated code fuses
   // (the device's own target -- gcnArchName without feature suffixes -- so the module always loads on it)
   const std::string off = "--offload-arch=" + arch;
-  const char* opts[] = {off.c_str(), "-O3", "-ffp-contract=off", "-std=c++17"};
-  const hiprtcResult rc = hiprtcCompileProgram(prog, 4, opts);
+  // PM_BRENT_UNIFORM: every pm_brent_init of these kernels takes kernel arguments (wave-uniform), which brent_core.h
+  // then pins in scalar registers once per item.  (PM_SERIAL_V0: the library built with it -- lib_exp/serial_v0.so --
+  // compiles its kernels with brent_core.h's earlier serial path as well.)
+#ifdef PM_SERIAL_V0
+  const char* opts[] = {off.c_str(), "-O3", "-ffp-contract=off", "-std=c++17", "-DPM_SERIAL_V0=1"};
+#else
+  const char* opts[] = {off.c_str(), "-O3", "-ffp-contract=off", "-std=c++17", "-DPM_BRENT_UNIFORM=1"};
+#endif
+  const hiprtcResult rc = hiprtcCompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
   if (rc != HIPRTC_SUCCESS) {
     size_t ls = 0;
     hiprtcGetProgramLogSize(prog, &ls);
