@@ -58,6 +58,13 @@
 #ifndef PM_QD_KIDSEQ
 #define PM_QD_KIDSEQ 0   // QUAD de novo hoisting: the two kids' lookups one kid at a time
 #endif
+#ifndef PM_QD_PIPE
+#define PM_QD_PIPE 1   // QUAD hoisting: slot s + 1's ring dwords fetched under slot s's arithmetic, the mutation-matrix rows once per item (0: neither)
+#endif
+#ifndef PM_QD_SKEW
+#define PM_QD_SKEW 0   // pipelined QUAD hoisting: the first PM_QD_SKEW slots' quartics deferred into the next slot, under its
+                       // lookups' latency (12: the most without scratch; 0.07 ms per step, within the runs' spread: opt-in)
+#endif
 #ifndef PM_QD_MONO
 #define PM_QD_MONO 1
 #endif
@@ -1159,9 +1166,13 @@ __device__ __forceinline__ void hoist_poly4_dn_pf(const DevArgs& A, const int* s
 #define QB 3          // slot buffers in the ring
 #endif
 #ifndef QD_AHEAD
+#if PM_QD_PIPE
+#define QD_AHEAD 3    // slots in flight ahead of the hoisting (<= QB: slot s's buffer is read during slot s - 1, hoist_quad_pipe_t)
+#else
 #define QD_AHEAD 2    // slots in flight ahead of the hoisting (< QB)
 #endif
-static_assert(QD_AHEAD >= 1 && QD_AHEAD < QB && QD_AHEAD <= 6, "QUAD ring geometry");
+#endif
+static_assert(QD_AHEAD >= 1 && QD_AHEAD < QB + (PM_QD_PIPE ? 1 : 0) && QD_AHEAD <= 6, "QUAD ring geometry");
 // s_waitcnt immediate for vmcnt(n) alone (expcnt and lgkmcnt at their no-wait maxima; vmcnt's two high bits at 15:14)
 #define PM_VMCNT(n) (0x0F70 | ((n) & 0xF) | (((n) >> 4) << 14))
 template <int N> __device__ __forceinline__ void vm_wait() { __builtin_amdgcn_s_waitcnt(PM_VMCNT(N)); }
@@ -1360,12 +1371,156 @@ __device__ __forceinline__ void hoist_quad_t(const DevArgs& A, const ItemCtx& I,
   }
 }
 
+// The lane's plane dwords of one slot buffer: w = planes g11, g12, g22, wg = planes 0-9 (de novo items only).
+template <bool DNV>
+__device__ __forceinline__ void quad_ring_read(const uint32_t* b, int o11, int o12, int o22, uint32_t* w, uint32_t* wg) {
+  w[0] = b[o11]; w[1] = b[o12]; w[2] = b[o22];
+  if constexpr (DNV)
+#pragma unroll
+    for (int g = 0; g < 10; g++) wg[g] = b[g * 64];
+}
+
+// hoist_quad_t as a two-stage pipeline (PM_QD_PIPE): the same operations in the same order on the same values, issued
+// so that no LDS round trip is waited for with an empty pipe.
+//  - Slot s + 1's 13 ring reads are issued at the top of slot s, ahead of slot s's table lookups.  LDS returns in
+//    order, so whatever wait lets slot s's first FMA start has also retired them, and slot s + 1 finds its dwords
+//    in registers (13 VGPRs live across the slot body).  Slot 0's are read before the loop: one exposed wait per item.
+//  - The item's 30 mutation-matrix entries are loaded once, before slot 0, and stay in SGPRs for the S slots (they are
+//    dead before the Brent loop).  No scalar load is then outstanding inside a slot, so the wait in front of the FMAs
+//    covers LDS operations only.  (It is still lgkmcnt(0) in every slot with an LDS-DMA outstanding -- the compiler's
+//    wait insertion drains the counter whenever one is pending -- and counted, lgkmcnt(14) down to 0 between the
+//    FMAs, only in the last two slots.  The one wait left per slot, for the lookups, has the DMA issue behind it;
+//    PM_QD_SKEW puts the previous slot's quartic there as well.)
+//  - Slot s + 1 has to have landed at the top of slot s, one slot body earlier than in hoist_quad_t, so the DMA runs
+//    QD_AHEAD = 3 slots ahead.  The ring stays at QB = 3 buffers: slot s + 3 overwrites slot s's buffer, whose reads
+//    were issued in slot s - 1 and whose last dword slot s's lookup addresses have consumed before the DMA is issued
+//    (the scheduling barrier between the lookups and the DMA keeps that order).
+template <int S, bool DNV, int NC>
+__device__ __forceinline__ void hoist_quad_pipe_t(const DevArgs& A, const ItemCtx& I, const uint8_t* pl, const double* lk,
+                                                  const double* M, double (*a)[NC], uint8_t* ring, const uint32_t* voff, double& m0, int& e0) {
+  if constexpr (NC == 4) { m0 = 1.0; e0 = 0; }
+  const int lane = threadIdx.x & 63;
+  const uint32_t* rw = (const uint32_t*)ring + lane;   // the lane's dword of plane g, slot buffer b: rw[(b * QSLOT + g * 256) / 4]
+  const int o11 = I.g11 * 64, o12 = I.g12 * 64, o22 = I.g22 * 64;
+  // re-read per item (opaque), so the compiler does not keep S slot predicates live across the Brent loop
+  int qfull = A.quad_full, nfam = A.n_fam, npo = A.n_person;
+  asm volatile("" : "+s"(qfull), "+s"(nfam), "+s"(npo));
+  // the item's three mutation-matrix rows from the kernel arguments, once: scalar FMA operands of every slot
+  double mr[3][10];
+  if constexpr (DNV) {
+#pragma unroll
+    for (int g = 0; g < 10; g++) { mr[0][g] = A.Mk[I.g11 * 10 + g]; mr[1][g] = A.Mk[I.g12 * 10 + g]; mr[2][g] = A.Mk[I.g22 * 10 + g]; }
+  }
+  uint32_t wn[3], wgn[10];   // the next slot's dwords
+  vm_wait_slots(QD_AHEAD - 1 < S - 1 ? QD_AHEAD - 1 : S - 1);   // slot 0 has landed
+  __builtin_amdgcn_sched_barrier(0);
+  quad_ring_read<DNV>(rw, o11, o12, o22, wn, wgn);
+  if constexpr (DNV) {   // pinned in SGPRs here (not re-loaded per slot)
+#pragma unroll
+    for (int g = 0; g < 10; g++) asm volatile("" : "+s"(mr[0][g]), "+s"(mr[1][g]), "+s"(mr[2][g]));
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  // a slot's quartic from its kid terms and parent likelihoods, into the slot's coefficient registers
+  auto finish = [&](int sp, const double (*D)[3], const double* lF, const double* lM) {
+    double q5x[5];
+    double* q5 = NC == 5 ? a[sp] : q5x;   // (NC = 5: the quartic straight into the slot's registers)
+    quad_poly4(D, lF, lM, q5);
+    if (sp >= qfull) {   // the partial last slot row: empty lanes hold the phantom family (f + g)^4
+      const bool empty = 64 * sp + lane >= nfam;
+      q5[0] = empty ? 1.0 : q5[0]; q5[1] = empty ? 4.0 : q5[1]; q5[2] = empty ? 6.0 : q5[2];
+      q5[3] = empty ? 4.0 : q5[3]; q5[4] = empty ? 1.0 : q5[4];
+    }
+    if constexpr (NC == 4) {   // (as hoist_quad_t)
+      double y = __builtin_amdgcn_rcp(q5[4]);
+      double ee = fma(-q5[4], y, 1.0);
+      y = fma(y, ee, y);
+      ee = fma(-q5[4], y, 1.0);
+      y = fma(y, ee, y);
+#pragma unroll
+      for (int k = 0; k < 4; k++) a[sp][k] = q5[k] * y;
+      int x;
+      m0 = frexp(m0 * q5[4], &x);
+      e0 += x;
+      asm volatile("" : "+v"(a[sp][0]), "+v"(a[sp][1]), "+v"(a[sp][2]), "+v"(a[sp][3]), "+v"(m0), "+v"(e0));
+    }
+  };
+  // PM_QD_SKEW: for the first PM_QD_SKEW slots, slot s's quartic (about 40 FP64 operations on 12 values held over)
+  // runs in slot s + 1, between the issue of that slot's lookups and the wait for them
+  constexpr bool SK = DNV && PM_QD_SKEW > 0;
+  double Dp[2][3], lFp[3], lMp[3];
+#pragma unroll
+  for (int s = 0; s < S; s++) {
+    if constexpr (DNV) PM_MARK("hoist_dn_slot_begin"); else PM_MARK("hoist_c7_slot_begin");
+    // byte j of a plane dword: person j of the family (0 father, 1 mother, 2 / 3 kids)
+    uint32_t w[3], wg[10];
+#pragma unroll
+    for (int k = 0; k < 3; k++) w[k] = wn[k];
+    if constexpr (DNV)
+#pragma unroll
+      for (int g = 0; g < 10; g++) wg[g] = wgn[g];
+    if (s + 1 < S) {
+      // slot s + 1 has landed: only the later slots' DMA (at most QD_AHEAD - 2 of them) may be outstanding
+      vm_wait_slots(QD_AHEAD - 2 < S - 2 - s ? QD_AHEAD - 2 : S - 2 - s);
+      __builtin_amdgcn_sched_barrier(0);
+      quad_ring_read<DNV>(rw + ((s + 1) % QB) * (QSLOT / 4), o11, o12, o22, wn, wgn);
+      __builtin_amdgcn_sched_barrier(0);   // older in LDS order than this slot's lookups
+    }
+    double lF[3], lM[3], D[2][3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { lF[k] = lk[w[k] & 0xFF]; lM[k] = lk[(w[k] >> 8) & 0xFF]; }
+    if constexpr (DNV) {
+      double pg[2][10];   // both kids' 20 table lookups in flight together
+#pragma unroll
+      for (int g = 0; g < 10; g++) { pg[0][g] = lk[(wg[g] >> 16) & 0xFF]; pg[1][g] = lk[wg[g] >> 24]; }
+      __builtin_amdgcn_sched_barrier(0);
+      if (s + QD_AHEAD < S) quad_dma(pl, s + QD_AHEAD, npo, voff, ring + ((s + QD_AHEAD) % QB) * QSLOT);
+      if (SK && s > 0 && s - 1 < PM_QD_SKEW) {   // the previous slot's quartic: arithmetic that needs none of the lookups in flight
+        finish(s - 1, Dp, lFp, lMp);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int q = 0; q < 2; q++) D[q][0] = D[q][1] = D[q][2] = 0.0;
+#pragma unroll
+      for (int g = 0; g < 10; g++) {   // CalcDenovoMutLk (:1553-1562), each matrix entry read once for both kids
+        const double m11 = mr[0][g], m12 = mr[1][g], m22 = mr[2][g];
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+          D[q][0] = fma(m11, pg[q][g], D[q][0]);
+          D[q][1] = fma(m12, pg[q][g], D[q][1]);
+          D[q][2] = fma(m22, pg[q][g], D[q][2]);
+        }
+      }
+    } else {   // cfg-7 items: likelihoodONEKid's autosomal terms on the item's three planes
+#pragma unroll
+      for (int q = 0; q < 2; q++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) D[q][k] = lk[(w[k] >> (16 + 8 * q)) & 0xFF];
+      __builtin_amdgcn_sched_barrier(0);
+      if (s + QD_AHEAD < S) quad_dma(pl, s + QD_AHEAD, npo, voff, ring + ((s + QD_AHEAD) % QB) * QSLOT);
+    }
+    if (SK && s + 1 < S && s < PM_QD_SKEW) {
+      // pinned here: otherwise the dot products sink into the next slot with the quartic, and their 20 lookups stay live
+      asm volatile("" : "+v"(D[0][0]), "+v"(D[0][1]), "+v"(D[0][2]), "+v"(D[1][0]), "+v"(D[1][1]), "+v"(D[1][2]));
+#pragma unroll
+      for (int k = 0; k < 3; k++) { lFp[k] = lF[k]; lMp[k] = lM[k]; Dp[0][k] = D[0][k]; Dp[1][k] = D[1][k]; }
+    } else finish(s, D, lF, lM);
+    if constexpr (DNV) PM_MARK("hoist_dn_slot_end"); else PM_MARK("hoist_c7_slot_end");
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // de novo items and cfg-7 items (uniform per item) take separate straight-line slot loops
 template <int S, int NC>
 __device__ __forceinline__ void hoist_quad(const DevArgs& A, const ItemCtx& I, const uint8_t* pl, const double* lk,
                                            const double* M, double (*a)[NC], uint8_t* ring, const uint32_t* voff, double& m0, int& e0) {
+#if PM_QD_PIPE
+  static_assert(!PM_QD_KIDSEQ, "PM_QD_KIDSEQ belongs to hoist_quad_t (PM_QD_PIPE=0)");
+  if (I.denovo) hoist_quad_pipe_t<S, true, NC>(A, I, pl, lk, M, a, ring, voff, m0, e0);
+  else hoist_quad_pipe_t<S, false, NC>(A, I, pl, lk, M, a, ring, voff, m0, e0);
+#else
   if (I.denovo) hoist_quad_t<S, true, NC>(A, I, pl, lk, M, a, ring, voff, m0, e0);
   else hoist_quad_t<S, false, NC>(A, I, pl, lk, M, a, ring, voff, m0, e0);
+#endif
 }
 
 // f = 1 (the generic-path de novo monomorphism item): L_fam(1) = a0, the f^4 coefficient; an empty slot's

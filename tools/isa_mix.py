@@ -9,7 +9,11 @@ vector memory -- of the whole kernel and of two regions:
                one Brent update.  Found from the control flow graph, so it needs no marker.
   hoist_slot   one slot row of the QUAD hoisting, between the assembler comments the source emits under -DPM_ISA_MARK
                ("; PM_MARK hoist_dn_slot_begin" / "_end", at hoist_quad_t's scheduling barriers): the per-slot list
-               and its median.
+               and its median, and per slot the path a full slot row executes (the cheapest path through the slot's
+               blocks: it branches around the clamped DMA addresses and the phantom family) with its VALU and
+               s_load counts and every s_waitcnt lgkmcnt on it: its count, the LDS / scalar loads it retires and
+               the number of VALU instructions between the last of those and the wait ("valu_gap": 0 = the wave
+               sits in the wait with nothing behind it; "ring_gap": the same from the last ring read it retires).
 
 The markers must not change the code: every instantiation is compiled with and without -DPM_ISA_MARK and the two
 whole-kernel and brent_loop mixes are compared ("markers_neutral").  The figures are static counts: the executed count
@@ -17,7 +21,8 @@ of a region is its static count only where the region is straight-line code (a h
 both update branches, so its executed path is shorter than its static size.
 
 The tool accounts for instruction classes only.  NAME: headline (64 x 16 QUAD --denovo), plain128 (128 x 16 plain PF, split trio / quad plan),
-or a k_brent template argument list in quotes.  -D switches (PM_SERIAL_V0=1: the earlier serial path) reach the compile.
+or a k_brent template argument list in quotes.  -D switches (PM_SERIAL_V0=1: the earlier serial path; PM_QD_PIPE=0: the
+earlier QUAD hoisting) reach the compile.
 """
 import argparse
 import json
@@ -179,6 +184,71 @@ def marked(lines, begin, end):
     return regions
 
 
+def marked_blocks(lines, begin, end):
+    """Like marked(), but each region as its basic blocks in layout order: [label or None, instruction lines]."""
+    regions, cur = [], None
+    for l in lines:
+        s = l.strip()
+        if "PM_MARK " + begin in s:
+            cur = [[None, []]]
+        elif "PM_MARK " + end in s and cur is not None:
+            regions.append(cur)
+            cur = None
+        elif cur is not None:
+            m = re.match(r"\.L(BB\d+_\d+):", l)
+            if m:
+                cur.append([m.group(1), []])
+            elif l.startswith("\t") and not s.startswith(".") and not s.startswith(";"):
+                cur[-1][1].append(s)
+    return regions
+
+
+def full_row_path(region):
+    """The instructions of the cheapest (fewest VALU) path from a slot region's first block to its end.  The region is
+    forward-branching code; a full slot row skips the clamped-address DMA and the phantom-family selects, which are the
+    only alternatives and both cost VALU instructions."""
+    idx = {b[0]: i for i, b in enumerate(region) if b[0]}
+    n = len(region)
+    succ = []
+    for i, (_, ins) in enumerate(region):
+        s = [idx[m.group(1)] for x in ins for m in [re.match(r"s_c?branch\w*\s+\.L(BB\d+_\d+)", x)] if m and m.group(1) in idx]
+        if not (ins and ins[-1].split()[0] == "s_branch"):
+            s.append(i + 1)   # fall-through (n: the region's end)
+        succ.append(s)
+    cost = [sum(1 for x in ins if classify(x.split()[0], x) == "valu") for _, ins in region]
+    best = [None] * (n + 1)
+    best[n] = (0, [])
+    for i in range(n - 1, -1, -1):
+        c = [(best[j][0], j) for j in succ[i] if j > i and best[j] is not None]
+        if c:
+            w, j = min(c)
+            best[i] = (cost[i] + w, [i] + best[j][1])
+    return [x for i in best[0][1] for x in region[i][1]]
+
+
+def slot_waits(path):
+    """Every s_waitcnt lgkmcnt of a slot's executed path with what it retires.  LDS operations return in order, so
+    lgkmcnt(n) retires all but the youngest n outstanding; with a scalar load outstanding (out of order) only
+    lgkmcnt(0) retires anything for certain."""
+    out, pending, valu = [], [], 0   # pending: (op, VALU count at its issue)
+    for l in path:
+        op = l.split()[0]
+        c = classify(op, l)
+        if c == "valu":
+            valu += 1
+        elif c in ("lds", "s_load"):
+            pending.append((op, valu))
+        elif c == "waitcnt_lgkm":
+            n = int(re.search(r"lgkmcnt\((\d+)\)", l).group(1))
+            smem = any(o.startswith("s_") for o, _ in pending)
+            done = pending if n == 0 else ([] if smem else pending[:len(pending) - n] if n < len(pending) else [])
+            pending = pending[len(done):]
+            ring = [v for o, v in done if o.startswith("ds_read") and not o.startswith("ds_read_b64")]
+            out.append({"lgkmcnt": n, "retires": len(done), "last": done[-1][0] if done else None,
+                        "valu_gap": valu - done[-1][1] if done else None, "ring_gap": valu - ring[-1] if ring else None})
+    return out
+
+
 def account(targs, defines):
     plain_lines, res = kernel_lines(compile_asm(targs, defines))
     mark_lines, res_m = kernel_lines(compile_asm(targs, defines + ["PM_ISA_MARK=1"]))
@@ -197,6 +267,9 @@ def account(targs, defines):
     if slots:
         out["hoist_slot"] = {"slots": len(slots), "valu_per_slot": [s["valu"] for s in slots],
                              "median": {k: statistics.median(s[k] for s in slots) for k in CLASSES}}
+        paths = [full_row_path(r) for r in marked_blocks(mark_lines, "hoist_dn_slot_begin", "hoist_dn_slot_end")]
+        out["hoist_slot"]["full_row"] = [{"valu": mix(p)["valu"], "s_load": mix(p)["s_load"], "lds": mix(p)["lds"],
+                                          "lgkm_waits": slot_waits(p)} for p in paths]
     return out
 
 
@@ -218,6 +291,10 @@ def main():
             print(f"  brent_loop  {l}")
         if "hoist_slot" in r:
             print(f"  hoist_slot  x{r['hoist_slot']['slots']} median " + "  ".join(f"{k}={v}" for k, v in r["hoist_slot"]["median"].items()))
+            for s, fr in enumerate(r["hoist_slot"]["full_row"]):
+                waits = " ".join(f"lgkmcnt({w['lgkmcnt']})<-{w['last']}+{w['valu_gap']}v" for w in fr["lgkm_waits"][:3])
+                more = len(fr["lgkm_waits"]) - 3
+                print(f"  slot {s:2d} full row: valu={fr['valu']} s_load={fr['s_load']} lds={fr['lds']}  {waits}" + (f" (+{more} waits)" if more > 0 else ""))
     if a.json:
         label = a.label or (",".join(a.defines) if a.defines else "default")
         doc = json.load(open(a.json)) if os.path.exists(a.json) else {}
