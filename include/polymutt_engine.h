@@ -338,14 +338,49 @@ int pm_engine_denovo_carriers(pm_engine *eng, pm_person_dn *top, pm_person_dn *a
  * n_cfg, maxidx, every other field and the genotype rows are those of the feature-off run, byte for byte.  Only the three
  * planes g11, g12, g22 of the block are read.  A de novo Brent that hits ITMAX is a stuck site like the standard one:
  * PM_EBRENT, pm_engine_stuck_site = the first site at which either stuck.
- * Not in the model: chrX/Y/MT sections (the autosomal transmission is wrong there: no DQ is computed, the results are
- * those of the feature-off run); indel records (the engine cannot tell them from SNVs: the host prints no tag for them);
+ * Not in the model: chrY/MT sections, and chrX sections unless pm_engine_set_vcf_denovo_chrx below is on (the autosomal
+ * transmission is wrong there: no DQ is computed, the results are those of the feature-off run); indel records (the engine cannot tell them from SNVs: the host prints no tag for them);
  * the fixed single-trio prior of the GLF path (it gives two homozygous-reference parents weight 0, hiding exactly the
  * event looked for).
  * on = 0 (the default): nothing is allocated or launched, every output byte is that of an engine without the feature.
  * PM_EINVAL: an engine without vcf_mode, or a submitted batch not yet collected.  pm_engine_set_denovo_families and
  * pm_engine_set_denovo_carriers keep refusing vcf_mode engines. */
 int pm_engine_set_vcf_denovo(pm_engine *eng, int32_t on);
+
+/* De novo calling on the chrX sections of a pm_engine_set_vcf_denovo engine: a sex-aware three-state model (additive to
+ * ABI 8: callers detect the feature by this symbol; no reference counterpart).  It takes effect on batches run while the
+ * current section is PM_CHR_X.  Alleles (a1, a2) = (ref, alt); states s = 0, 1, 2 = a1a1, a1a2, a2a2 with GLF indices
+ * g = (g11, g12, g22).  A male uses states 0 and 2 only, as hemizygous a1 and a2; sex 0 (unknown) is treated as female, as
+ * the standard chrX model does.
+ *   M3[x][y]       = M[g[x]][g[y]], M the 10 x 10 genotype mutation matrix above;
+ *   A4             = the 4 x 4 allele mutation matrix M is built from (GenotypeMutationModel: diagonal 1 - mu, a transition
+ *                    mu r / (1 + r), each transversion mu 0.5 / (1 + r); mu = denovo_mut_rate, r = denovo_tstv);
+ *   H3             = the haploid mutation matrix on the three states: H3[0][0] = A4[a1][a1], H3[0][2] = A4[a1][a2],
+ *                    H3[2][0] = A4[a2][a1], H3[2][2] = A4[a2][a2], row 1 and column 1 zero;
+ *   T_F, T_M       = the chrX bi-allelic transmissions to a daughter and to a son (SetTransmissionMatrix_BA_CHRX_2Female,
+ *                    _2Male), [father][mother][child];
+ *   Tdn_F[i][j][k] = Sum_m T_F[i][j][m] M3[m][k],   Tdn_M[i][j][k] = Sum_m T_M[i][j][m] H3[m][k].
+ * Founder priors in the frequency f: a male (f, 0, 1 - f), everyone else (f^2, 2 f (1 - f), (1 - f)^2) -- those of the
+ * standard chrX objective.
+ * L^dn_X(f) routes the families as vcf_mode does on chrX: a founders-only family is the product of its persons (a male
+ * f l11 + (1 - f) l22, everyone else the Hardy-Weinberg quadratic); every family with offspring, nuclear ones included,
+ * goes through the bi-allelic peel (there is no closed form on X).  Type-1 steps use Tdn of the child's sex; type-3 steps
+ * use Tdn of the child's sex without a marriage partial and plain T of the child's sex with one (the
+ * FamilyLikelihoodES.cpp:1391 quirk the autosomal feature keeps); type-2 steps are unchanged.
+ * Outputs per called site of a chrX section, in the autosomal feature's fields: varllk[2] = N = max_f log10 L^dn_X(f) by
+ * the same OptimizeFrequency + Brent, varfreq[2] its maximiser, evals[2] its evaluation count, denovo_lr = N - D with D
+ * the standard chrX objective (M3 = H3 = identity, plain T) evaluated once at varfreq[1] by the same kernel with the same
+ * log10.  Every other result field and the genotype rows are those of the feature-off run, byte for byte; only the three
+ * planes g11, g12, g22 are read.  A de novo Brent that hits ITMAX is a stuck site like any other.  FP64, a fixed
+ * reduction order and no floating-point atomics: the same input gives the same bytes.
+ * Not in the model: chrY and MT sections (no DQ, as before); pseudo-autosomal regions (ignored, as in the standard chrX
+ * model); the per-family and per-child detail, which stays autosomal only -- pm_engine_vcf_denovo_rows keeps returning 0
+ * rows on chrX sections.
+ * on = 0 (the default): nothing is allocated or launched, every output byte is that of an engine without the feature.
+ * It may be set at any point between batches.  PM_EINVAL: an engine without vcf_mode, pm_engine_set_vcf_denovo not on, or a
+ * submitted batch not yet collected.  pm_engine_set_vcf_denovo(eng, 0) switches this off too (and so does a repeated
+ * pm_engine_set_vcf_denovo(eng, 1), which rebuilds that feature: set this switch after it). */
+int pm_engine_set_vcf_denovo_chrx(pm_engine *eng, int32_t on);
 
 /* The families and the children behind each DQ of pm_engine_set_vcf_denovo (vcf_mode engines; additive to ABI 8: callers
  * detect the feature by these symbols; no reference counterpart).  A row is a called site (status == 0) of an autosomal

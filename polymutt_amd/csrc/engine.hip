@@ -135,6 +135,11 @@ struct pm_engine {
   size_t vdn_lds = 0;        // dynamic LDS of k_vdn_brent (the hoisted coefficients), 0: they live in d_vdn_co
   int* d_vdn_terms = nullptr;
   double *d_vdn_co = nullptr, *d_vdn_ws = nullptr;
+  // its chrX model (pm_engine_set_vcf_denovo_chrx): off = no buffer, no launch
+  bool vdnx_on = false;
+  int vdnx_T = 0, vdnx_grid = 0, vdnx_terms = 0, vdnx_peel = 0;
+  int* d_vdnx_terms = nullptr;
+  double* d_vdnx_ws = nullptr;
   // the families and children behind each DQ (pm_engine_set_vcf_denovo_detail): off (both k 0) = no buffer, no launch
   int vw_fam_k = 0, vw_car_k = 0, vw_grid = 0, vw_n_nuc = 0, vw_n_es = 0;
   int vw_rows = 0;            // rows of the last finished batch (after PM_EBRENT: those before the stuck site)
@@ -149,7 +154,7 @@ struct pm_engine {
   std::vector<int> fam_kind_h, fam_perm_h;
   std::vector<int32_t> fa_h, mo_h;  // family-local parent indices (-1: none)
   unsigned long long* d_counters = nullptr;
-  double M_h[100];
+  double M_h[100], A4_h[16];   // the genotype mutation matrix and the allele one it is built from
   // stats
   pm_kernel_stats stats{};
   std::vector<std::pair<hipEvent_t, hipEvent_t>> brent_events;
@@ -159,13 +164,14 @@ struct pm_engine {
   bool es_ops_known = false;           // (the compiled kernels report them; the generic k_es_hoist does not)
 };
 
-static void geno_mut_matrix(double mu, double tstv, double* out) {   // src/MutationModel.cpp:15-90
+static void geno_mut_matrix(double mu, double tstv, double* out, double* a4) {   // src/MutationModel.cpp:15-90
   double A[4][4];
   for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) A[i][j] = (i == j) ? 1 - mu : (1 - mu) / 3;
   if (tstv != 0.0) {
     A[0][2] = A[2][0] = A[1][3] = A[3][1] = mu / 3 * (3 - 3 / (1 + tstv));
     A[0][1] = A[0][3] = A[1][0] = A[1][2] = A[2][1] = A[2][3] = A[3][0] = A[3][2] = mu / 3 * (0.5 / (1 + tstv) * 3);
   }
+  for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) a4[i * 4 + j] = A[i][j];
   double R[16][16];
   int from = -1;
   for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) {
@@ -366,7 +372,7 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_items[0], E->d_items[1], E->d_items[2], E->d_counts, E->d_eval_total, E->d_row_site,
                   E->d_counters, E->d_row_blk, E->d_qctr, E->d_fam_top, E->d_fam_sum, E->d_fam_all, E->d_fam_line,
                   E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf,
-                  E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws, E->d_vw_row_site, E->d_vw_pfam, E->d_vw_fam_top, E->d_vw_fam_sum,
+                  E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws, E->d_vdnx_terms, E->d_vdnx_ws, E->d_vw_row_site, E->d_vw_pfam, E->d_vw_fam_top, E->d_vw_fam_sum,
                   E->d_vw_fam_all, E->d_vw_fam_line, E->d_vw_car_top, E->d_vw_car_all, E->d_vw_car_line, E->d_vw_kids, E->d_vw_is_kid,
                   E->d_vw_jbuf};
   for (void* b : bufs) if (b) hipFree(b);
@@ -526,7 +532,7 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
   for (int i = 0; i <= 255; i++) lk[i] = pow(0.1, i * 0.1);   // core/BaseQualityHelper.cpp:13 (host glibc)
   if (E->vcf)   // FamilyLikelihoodSeq_VCF::PL2LK_table (src/FamilyLikelihoodSeq_VCF.cpp:21-22)
     for (int i = 0; i <= 255; i++) lk[i] = pow(10, -double(i) / 10.0);
-  geno_mut_matrix(par->denovo_mut_rate, par->denovo_tstv, E->M_h);
+  geno_mut_matrix(par->denovo_mut_rate, par->denovo_tstv, E->M_h, E->A4_h);
   static pm_synth_tables syn;
   pm_synth_build_tables(&syn);
   std::vector<int32_t> fa(ped->n_person, -1), mo(ped->n_person, -1);
@@ -1141,6 +1147,22 @@ static int launch_vcf_denovo(pm_engine* E, const DevArgs& A) {
   return PM_OK;
 }
 
+// The same on a chrX section (pm_engine_set_vcf_denovo_chrx): k_vdn_brent_x on its own terms and workspace, then
+// k_finalize_vdn as it is.  No detail rows on X: counts[10] stays 0.
+static int launch_vcf_denovo_x(pm_engine* E, const DevArgs& A) {
+  VdnXArgs V;
+  V.terms = E->d_vdnx_terms; V.n_terms = E->vdnx_terms; V.n_peel = E->vdnx_peel; V.ws = E->d_vdnx_ws;
+  for (int i = 0; i < 16; i++) V.a4[i] = E->A4_h[i];
+  const int grid = std::max(1, std::min(E->vdnx_grid, A.n));
+  if (int rc = mark(E, E->brent_events, true)) return rc;
+  hipLaunchKernelGGL(E->vdnx_T == 64 ? k_vdn_brent_x<64> : k_vdn_brent_x<256>, dim3(grid), dim3(E->vdnx_T), 0, E->stream, A, V);
+  HIP_TRY(hipGetLastError());
+  if (int rc = mark(E, E->brent_events, false)) return rc;
+  hipLaunchKernelGGL(k_finalize_vdn, dim3((A.n + 255) / 256), dim3(256), 0, E->stream, A);
+  HIP_TRY(hipGetLastError());
+  return PM_OK;
+}
+
 static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* dm, const uint8_t* ref, pm_site_result* res,
                         pm_geno_call* calls) {
   DevArgs A = make_args(E, n, pl, dm, ref, res, calls);
@@ -1187,6 +1209,7 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
     hipLaunchKernelGGL(k_finalize_vcf, dim3(gb), dim3(tb), 0, E->stream, A);
     HIP_TRY(hipGetLastError());
     if (E->vdn_on && E->chrom == PM_CHR_AUTO && (rc = launch_vcf_denovo(E, A))) return rc;
+    if (E->vdnx_on && E->chrom == PM_CHR_X && (rc = launch_vcf_denovo_x(E, A))) return rc;
   } else {
     hipLaunchKernelGGL(k_select, dim3(gb), dim3(tb), 0, E->stream, A);
     HIP_TRY(hipGetLastError());
@@ -1368,6 +1391,14 @@ static void vw_free(pm_engine* E) {
   for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
 }
 
+// pm_engine_set_vcf_denovo_chrx's buffers (the stream is idle)
+static void vdnx_free(pm_engine* E) {
+  E->vdnx_on = false;
+  if (E->d_vdnx_terms) (void)hipFree(E->d_vdnx_terms);
+  if (E->d_vdnx_ws) (void)hipFree(E->d_vdnx_ws);
+  E->d_vdnx_terms = nullptr; E->d_vdnx_ws = nullptr;
+}
+
 int pm_engine_set_vcf_denovo(pm_engine* E, int32_t on) {
   if (!E) { pm_set_last_error("pm_engine_set_vcf_denovo: invalid arguments"); return PM_EINVAL; }
   if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_denovo: the engine was created without vcf_mode"); return PM_EINVAL; }
@@ -1375,6 +1406,7 @@ int pm_engine_set_vcf_denovo(pm_engine* E, int32_t on) {
   HIP_TRY(hipSetDevice(E->device));
   HIP_TRY(hipStreamSynchronize(E->stream));
   E->vdn_on = false;
+  vdnx_free(E);
   void** bufs[] = {(void**)&E->d_vdn_terms, (void**)&E->d_vdn_co, (void**)&E->d_vdn_ws};
   for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
   if (!on) { vw_free(E); return PM_OK; }
@@ -1416,6 +1448,59 @@ int pm_engine_set_vcf_denovo(pm_engine* E, int32_t on) {
     return rc;
   HIP_TRY(hipMemcpy(E->d_vdn_terms, terms.data(), sizeof(int) * terms.size(), hipMemcpyHostToDevice));
   E->vdn_on = true;
+  return PM_OK;
+}
+
+int pm_engine_set_vcf_denovo_chrx(pm_engine* E, int32_t on) {
+  if (!E) { pm_set_last_error("pm_engine_set_vcf_denovo_chrx: invalid arguments"); return PM_EINVAL; }
+  if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_denovo_chrx: the engine was created without vcf_mode"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_vcf_denovo_chrx: a submitted batch has not been collected"); return PM_EINVAL; }
+  if (!E->vdn_on) {
+    pm_set_last_error("pm_engine_set_vcf_denovo_chrx: needs pm_engine_set_vcf_denovo(engine, 1) first (vcf_denovo is off)");
+    return PM_EINVAL;
+  }
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  vdnx_free(E);
+  if (!on) return PM_OK;
+  // the objective's terms, routed like vcf_mode's plan 1 on chrX: every family with offspring is peeled (nuclear ones
+  // included: no closed form), founders-only families give their persons
+  std::vector<int> terms, pers;
+  int ws_need = 0;   // doubles per lane of the largest peel: partials [n][3] + marriage partials [slots][9]
+  for (int f = 0; f < E->n_fam; f++) {
+    if (E->fam_kind_h[f] == PM_FAM_FOUNDERS) { for (int p = E->fam_start_h[f]; p < E->fam_start_h[f + 1]; p++) pers.push_back(p); continue; }
+    if (E->peel_start_h[f + 1] == E->peel_start_h[f]) {
+      pm_set_last_error("pm_engine_set_vcf_denovo_chrx: a family with offspring has no peeling schedule (pm_pedigree.steps)");
+      return PM_EPED;
+    }
+    int slots = 0;
+    for (int s = E->peel_start_h[f]; s < E->peel_start_h[f + 1]; s++) {
+      const int slot = (E->steps_h[s].y >> 8) & 255;
+      if (slot != 255) slots = std::max(slots, slot + 1);
+    }
+    ws_need = std::max(ws_need, (E->fam_start_h[f + 1] - E->fam_start_h[f]) * 3 + slots * 9);
+    terms.push_back(f);
+  }
+  if (ws_need > E->ws_per_lane) {   // (a vcf_mode engine packs every family's schedule, nuclear ones included)
+    pm_set_last_error("pm_engine_set_vcf_denovo_chrx: the peel workspace per lane does not cover a family's peel");
+    return PM_EPED;
+  }
+  E->vdnx_peel = (int)terms.size();
+  terms.insert(terms.end(), pers.begin(), pers.end());
+  E->vdnx_terms = (int)terms.size();
+  E->vdnx_T = E->vdnx_terms <= 128 ? 64 : 256;
+  // k_vdn_brent's grid rule (its static LDS only) and 1 GiB workspace cap
+  E->vdnx_grid = E->n_cu * std::max(1, std::min(1024 / E->vdnx_T, (160 * 1024) / (4 * 1024)));
+  const size_t ws_block = (size_t)E->ws_per_lane * E->vdnx_T * sizeof(double);
+  if (ws_block > 0) E->vdnx_grid = (int)std::max<size_t>(1, std::min<size_t>(E->vdnx_grid, ((size_t)1 << 30) / ws_block));
+  E->vdnx_grid = std::min(E->vdnx_grid, E->max_batch);
+  int rc;
+  if ((rc = dalloc(&E->d_vdnx_terms, terms.size())) || (rc = dalloc(&E->d_vdnx_ws, (size_t)E->vdnx_grid * E->ws_per_lane * E->vdnx_T))) {
+    vdnx_free(E);
+    return rc;
+  }
+  HIP_TRY(hipMemcpy(E->d_vdnx_terms, terms.data(), sizeof(int) * terms.size(), hipMemcpyHostToDevice));
+  E->vdnx_on = true;
   return PM_OK;
 }
 

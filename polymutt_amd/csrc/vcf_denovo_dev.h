@@ -1,5 +1,6 @@
 // vcf_denovo_dev.h -- de novo calling on the --in_vcf path (pm_engine_set_vcf_denovo): the three-genotype mutation model of
-// include/polymutt_engine.h, one more Brent item per called autosomal site.  Included by engine.hip after engine_dev.h.
+// include/polymutt_engine.h, one more Brent item per called autosomal site -- and, behind pm_engine_set_vcf_denovo_chrx, per
+// called chrX site (k_vdn_brent_x, a kernel of its own below).  Included by engine.hip after engine_dev.h.
 //
 // On a biallelic record only the genotypes g = (g11, g12, g22) of (ref, alt) carry data, so the 10 x 10 genotype
 // mutation matrix M collapses to M3[x][y] = M[g[x]][g[y]] and the de novo transmission to
@@ -266,6 +267,180 @@ __global__ void __launch_bounds__(256) k_finalize_vdn(DevArgs A) {
   R->varfreq[2] = A.minv[site * 8 + 2];
   R->evals[2] = A.evals[site * 8 + 2];
   R->denovo_lr = N - A.raw[(size_t)site * 8 + 3];
+}
+
+// ------------------------------------------------------------------------------------------------
+// chrX (pm_engine_set_vcf_denovo_chrx): the sex-aware three-state model of include/polymutt_engine.h.  A male carries the
+// states 0 and 2 only (hemizygous a1, a2), so a son's transmission c_TBA[2] is followed by the haploid mutation matrix
+// H3 (the 2 x 2 block of the allele mutation matrix A4 on states 0 and 2, row and column 1 zero) and a daughter's
+// c_TBA[1] by M3; male founders take the prior (f, 0, 1 - f).  There is no closed form on X: every family with offspring
+// is peeled on every evaluation (vcf_mode's plan 1 routing), a founders-only family is the product of its persons.
+__device__ __forceinline__ int vdn_pick3(const int* g, int s);
+struct VdnXArgs {
+  const int* terms;   // [n_terms] n_peel peeled families (every family with offspring), then the persons of founders-only families
+  int n_terms, n_peel;
+  double* ws;         // peel workspace [grid][ws_per_lane][T], lane-interleaved like DevArgs::ws
+  double a4[16];      // the allele mutation matrix of denovo_mut_rate / denovo_tstv (the one M is built from)
+};
+
+// d_es_lk<3> on chrX with the transmission tables passed in (LDS), picked by the sex of the step's child: t[0] to a
+// daughter (or a child of unknown sex), t[27] to a son.  tdn where the de novo model mutates, tpl (plain) elsewhere.
+__device__ __forceinline__ double d_es_lk3_vdn_x(const DevArgs& A, int f, const uint8_t* pl, const double* lk, const int* gidx, double freq,
+                                                 const double* tdn, const double* tpl, double* ws, size_t st) {
+  const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0, nf = A.fam_founders[f];
+#define PP(i, j) ws[((size_t)(i) * 3 + (j)) * st]
+#define MPP(sl, x, y) ws[((size_t)n * 3 + (size_t)(sl) * 9 + (x) * 3 + (y)) * st]
+  const size_t np = (size_t)A.n_person;
+  for (int i = 0; i < n; i++) {
+    const bool fo = A.is_founder[p0 + i] != 0;
+    const uint8_t* R = pl + p0 + i;   // plane g at R[g * n_person]
+    double pr[3] = {0.0, 0.0, 0.0};
+    if (i < nf) {
+      pr[0] = freq * freq; pr[1] = 2 * freq * (1 - freq); pr[2] = (1 - freq) * (1 - freq);
+      if (A.sex[p0 + i] == MALE) { pr[0] = freq; pr[1] = 0; pr[2] = 1 - freq; }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const double pen = lk[R[gidx[j] * np]];
+      PP(i, j) = fo ? pr[j] * pen : pen;
+    }
+  }
+  const int s0 = A.peel_start[f], s1 = A.peel_start[f + 1];
+  for (int s = s0; s < s1; s++) {
+    const int2 S = A.steps[s];
+    const int type = S.x & 255, from0 = (S.x >> 8) & 255, from1 = (S.x >> 16) & 255, to0 = (S.x >> 24) & 255;
+    const int slot = (S.y >> 8) & 255, create = (S.y >> 16) & 1, fa2mo = (S.y >> 17) & 1;
+    if (type == 1) {   // offspring -> parents: transmission_denovo of the child's sex
+      if (create)
+        for (int x = 0; x < 9; x++) MPP(slot, x / 3, x % 3) = 1.0;
+      const double* tt = tdn + (A.sex[p0 + from0] == MALE ? 27 : 0);
+      double pk[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) pk[k] = PP(from0, k);
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+          double sum = 0;
+#pragma unroll
+          for (int k = 0; k < 3; k++) sum += tt[(i * 3 + j) * 3 + k] * pk[k];
+          MPP(slot, i, j) *= sum;
+        }
+    } else if (type == 2) {   // spouse -> spouse
+      double ps[3];
+#pragma unroll
+      for (int j = 0; j < 3; j++) ps[j] = PP(from0, j);
+      for (int i = 0; i < 3; i++) {
+        double sum = 0.0;
+        if (slot == 255) for (int j = 0; j < 3; j++) sum += ps[j];
+        else if (fa2mo) for (int j = 0; j < 3; j++) sum += ps[j] * MPP(slot, j, i);
+        else for (int j = 0; j < 3; j++) sum += ps[j] * MPP(slot, i, j);
+        PP(to0, i) *= sum;
+      }
+    } else {   // parents -> only offspring: transmission_denovo without a marriage partial, plain transmission with one
+      const double* tt = (slot == 255 ? tdn : tpl) + (A.sex[p0 + to0] == MALE ? 27 : 0);
+      double pf[3], pm[3], sum[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) { pf[k] = PP(from0, k); pm[k] = PP(from1, k); sum[k] = 0.0; }
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+          const double w = (slot == 255) ? pf[i] * pm[j] : pf[i] * MPP(slot, i, j) * pm[j];
+#pragma unroll
+          for (int k = 0; k < 3; k++) sum[k] += w * tt[(i * 3 + j) * 3 + k];
+        }
+#pragma unroll
+      for (int k = 0; k < 3; k++) PP(to0, k) *= sum[k];
+    }
+  }
+  const int fin = (A.steps[s1 - 1].x >> 24) & 255;
+  double L = 0.0;
+  for (int i = 0; i < 3; i++) L += PP(fin, i);
+  return L;
+#undef PP
+#undef MPP
+}
+
+// The chrX de novo Brent item of every site of list 0: k_vdn_brent's outputs (raw / minv / evals slot 2, D to raw slot 3,
+// a stuck Brent to counts[5] / counts[6]) for k_finalize_vdn.  One block per item, the terms round robin over its threads.
+template <int T>
+__global__ void __launch_bounds__(T) k_vdn_brent_x(DevArgs A, VdnXArgs V) {
+  __shared__ double s_lk[256];
+  __shared__ double s_tpl[54], s_tdn[54], s_m3[9], s_h3[9];   // [0..26] to a daughter, [27..53] to a son
+  __shared__ double s_red[T > 64 ? 96 : 1];
+  __shared__ int s_rede[T > 64 ? 32 : 1];
+  for (int i = threadIdx.x; i < 256; i += T) s_lk[i] = A.lktab[i];
+  if (threadIdx.x < 54) s_tpl[threadIdx.x] = c_TBA[1 + threadIdx.x / 27][threadIdx.x % 27];
+  double* ws = V.ws + (size_t)blockIdx.x * A.ws_per_lane * T + threadIdx.x;
+  const int nItems = A.counts[0];
+  const int* items = A.items[0];
+  const size_t np = (size_t)A.n_person;
+  int par = 0;
+  unsigned long long ev_acc = 0;
+  for (int it = blockIdx.x; it < nItems; it += gridDim.x) {
+    const int site = items[it] >> 3;
+    const int r = A.ref[site];
+    const int a1 = r & 15, a2 = r >> 4;
+    const int gidx[3] = {d_gi(a1, a1), d_gi(a1, a2), d_gi(a2, a2)};
+    const uint8_t* pl = A.pl + (size_t)site * np * 10;
+    __syncthreads();   // (the tables of the block's previous item are no longer read; s_tpl is written)
+    if (threadIdx.x < 9) {
+      const int x = threadIdx.x / 3, y = threadIdx.x % 3;
+      s_m3[threadIdx.x] = A.M[vdn_pick3(gidx, x) * 10 + vdn_pick3(gidx, y)];
+      s_h3[threadIdx.x] = (x == 1 || y == 1) ? 0.0 : V.a4[(((x ? a2 : a1) - 1) & 3) * 4 + (((y ? a2 : a1) - 1) & 3)];   // (bases are 1..4)
+    }
+    __syncthreads();
+    if (threadIdx.x < 54) {
+      const int ij = (threadIdx.x % 27) / 3, k = threadIdx.x % 3;
+      const double* tp = s_tpl + (threadIdx.x < 27 ? 0 : 27);
+      const double* mm = threadIdx.x < 27 ? s_m3 : s_h3;
+      double s = 0.0;
+      for (int m = 0; m < 3; m++) s += tp[ij * 3 + m] * mm[m * 3 + k];
+      s_tdn[threadIdx.x] = s;
+    }
+    __syncthreads();
+    // Two passes over the same code, as in k_vdn_brent: pass 0 the standard chrX objective (plain T everywhere) once at
+    // the standard item's maximiser for D; pass 1 the de novo objective through Brent for N.
+    const double f_std = A.minv[site * 8 + 1];
+    double d_std = 0.0;
+    PmBrent B;
+    for (int pass = 0; pass < 2; pass++) {
+      const bool dn = pass != 0;
+      const double* tt = dn ? s_tdn : s_tpl;
+      pm_brent_init(B, A.precision, A.itmax);
+      if (!dn) B.x = f_std;
+      for (;;) {
+        const double x = B.x, g = 1 - x;
+        double m = 1.0;
+        int e = 0;
+        for (int q = threadIdx.x; q < V.n_peel; q += T) {
+          int e1, e2;
+          const double mv = frexp(d_es_lk3_vdn_x(A, V.terms[q], pl, s_lk, gidx, x, tt, s_tpl, ws, T), &e1);
+          m = frexp(m * mv, &e2);
+          e += e1 + e2;
+        }
+        for (int q = V.n_peel + threadIdx.x; q < V.n_terms; q += T) {   // lkSinglePerson: a male is hemizygous
+          const int p = V.terms[q];
+          const uint8_t* P = pl + p;
+          const double l11 = s_lk[P[gidx[0] * np]], l12 = s_lk[P[gidx[1] * np]], l22 = s_lk[P[gidx[2] * np]];
+          const double v = A.sex[p] == MALE ? l11 * x + l22 * g : l11 * (x * x) + l12 * (2 * x * g) + l22 * (g * g);
+          int e1, e2;
+          const double mv = frexp(v, &e1);
+          m = frexp(m * mv, &e2);
+          e += e1 + e2;
+        }
+        const double tot = vdn_logprod<T>(m, e, s_red, s_rede, par);
+        if (!dn) { d_std = tot; break; }
+        if (!pm_brent_feed(B, -tot)) break;
+      }
+    }
+    if (threadIdx.x == 0) {
+      A.raw[(size_t)site * 8 + 3] = d_std;
+      A.raw[(size_t)site * 8 + 2] = -B.fmin;
+      A.minv[site * 8 + 2] = B.mn;
+      A.evals[site * 8 + 2] = B.nev;
+      ev_acc += B.nev - 1;   // (f(a) and f(c) are counted, not computed; one evaluation for D)
+      if (!B.ok) { atomicExch(&A.counts[5], 1); atomicMin(&A.counts[6], site); }
+    }
+  }
+  if (threadIdx.x == 0 && ev_acc) atomicAdd(A.eval_total, ev_acc);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -127,6 +127,7 @@ EXPORTS = {
     "pm_engine_set_denovo_carriers": (i32, [C.c_void_p, i32, i32]),
     "pm_engine_denovo_carriers": (i32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_engine_set_vcf_denovo": (i32, [C.c_void_p, i32]),
+    "pm_engine_set_vcf_denovo_chrx": (i32, [C.c_void_p, i32]),
     "pm_engine_set_vcf_denovo_detail": (i32, [C.c_void_p, i32, i32, i32]),
     "pm_engine_vcf_denovo_rows": (i32, [C.c_void_p, P(i32), C.c_void_p]),
     "pm_engine_vcf_denovo_families": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -426,6 +427,13 @@ class Engine:
         if not on:   # (the engine switches the detail off with it)
             self._vw_fam_k = self._vw_car_k = 0
             self._vw_all = False
+
+    def set_vcf_denovo_chrx(self, on=True):
+        """pm_engine_set_vcf_denovo_chrx (after set_vcf_denovo(True)): batches run on a PM_CHR_X section get N, its
+        maximiser, its evaluation count and DQ from the sex-aware three-state chrX model (hemizygous males, the
+        transmission picked by the child's sex); off (the default) leaves every output byte as it was.
+        Any later set_vcf_denovo call switches it off again.  The per-family / per-child detail stays autosomal only."""
+        self._check(self.lib.pm_engine_set_vcf_denovo_chrx(self.h, 1 if on else 0))
 
     def set_vcf_denovo_detail(self, fam_k, car_k, want_all=False):
         """pm_engine_set_vcf_denovo_detail (after set_vcf_denovo(True)): per row -- a called autosomal site whose DQ is at

@@ -50,7 +50,7 @@ Options parse_command_line(int argc, char** argv) {
       {"in_blocks", 's', &o.blocksIn}, {"glf2blocks", 's', &o.blocksOut}, {"block_sites", 'i', &o.blockSites}, {"exact_log10", 'b', &o.exact_log10}, {"numerics", 's', &o.numerics},
       {"denovo_families", 'i', &o.denovo_families}, {"denovo_carriers", 'i', &o.denovo_carriers},
       {"vcf_denovo", 'b', &o.vcf_denovo}, {"vcf_denovo_families", 'i', &o.vcf_denovo_families},
-      {"vcf_denovo_carriers", 'i', &o.vcf_denovo_carriers},
+      {"vcf_denovo_carriers", 'i', &o.vcf_denovo_carriers}, {"vcf_denovo_chrX", 'b', &o.vcf_denovo_chrX},
   };
   auto assign = [](Flag& f, const char* v) {
     switch (f.kind) {
@@ -103,6 +103,7 @@ Options parse_command_line(int argc, char** argv) {
     if (o.denovo_families < 1 || o.denovo_families > 8) throw FatalError("--denovo_families takes a family count from 1 to 8\n");
   }
   if (o.vcf_denovo && o.vcfInFile.empty()) throw FatalError("--vcf_denovo needs --in_vcf\n");
+  if (o.vcf_denovo_chrX && !o.vcf_denovo) throw FatalError("--vcf_denovo_chrX needs --vcf_denovo\n");
   if (o.vcf_denovo_families_given) {
     if (!o.vcf_denovo) throw FatalError("--vcf_denovo_families needs --vcf_denovo\n");
     if (o.vcf_denovo_families < 1 || o.vcf_denovo_families > 8) throw FatalError("--vcf_denovo_families takes a family count from 1 to 8\n");

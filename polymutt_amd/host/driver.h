@@ -40,6 +40,9 @@ struct Options {
   // mutation (DNC / DNCP / DNCE), in the formats of --denovo_families / --denovo_carriers (pm_engine_set_vcf_denovo_detail)
   int vcf_denovo_families = 0, vcf_denovo_carriers = 0;
   bool vcf_denovo_families_given = false, vcf_denovo_carriers_given = false;
+  // --vcf_denovo_chrX (with --vcf_denovo): biallelic SNV records of the --chrX chromosome get ;DQ= too, from the sex-aware
+  // three-state chrX model (pm_engine_set_vcf_denovo_chrx); DQ alone: the DNF / DNC detail stays autosomal only
+  bool vcf_denovo_chrX = false;
   std::string cmd;
   pm_params params() const;
 };
@@ -93,6 +96,8 @@ class SiteEvaluator {
   virtual void denovo_carriers(pm_person_dn* top) { (void)top; throw FatalError("--denovo_carriers needs the GPU engine\n"); }
   // --vcf_denovo: once, before the first batch; the results then carry DQ in denovo_lr (pm_engine_set_vcf_denovo)
   virtual void set_vcf_denovo(bool on) { (void)on; throw FatalError("--vcf_denovo is not supported by this evaluator\n"); }
+  // --vcf_denovo_chrX: once, after set_vcf_denovo(true) and before the first batch (pm_engine_set_vcf_denovo_chrx)
+  virtual void set_vcf_denovo_chrx(bool on) { (void)on; throw FatalError("--vcf_denovo_chrX is not supported by this evaluator\n"); }
   // --vcf_denovo_families / --vcf_denovo_carriers: set_vcf_denovo_detail once, after set_vcf_denovo(true) and before the
   // first batch; then, for the batch the last run_vcf() returned (also after it threw a BrentError: the rows before the
   // stuck site), vcf_denovo_rows returns the row count and writes the rows' batch indices to site (may be null), and the

@@ -119,6 +119,9 @@ class EngineEvaluator : public SiteEvaluator {
   void set_vcf_denovo(bool on) override {
     for (auto* e : eng_) check(pm_engine_set_vcf_denovo(e, on ? 1 : 0));
   }
+  void set_vcf_denovo_chrx(bool on) override {
+    for (auto* e : eng_) check(pm_engine_set_vcf_denovo_chrx(e, on ? 1 : 0));
+  }
   void set_vcf_denovo_detail(int fam_k, int car_k) override {
     for (auto* e : eng_) check(pm_engine_set_vcf_denovo_detail(e, fam_k, car_k, 0));
   }

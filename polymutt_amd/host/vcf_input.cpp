@@ -374,6 +374,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   const double tstv = 2.0, prior_ts = tstv / (tstv + 1), prior_tv = 0.5 / (tstv + 1);
 
   if (opt.vcf_denovo) eval.set_vcf_denovo(true);
+  if (opt.vcf_denovo && opt.vcf_denovo_chrX) eval.set_vcf_denovo_chrx(true);
   const int dnf_k = opt.vcf_denovo ? opt.vcf_denovo_families : 0, dnc_k = opt.vcf_denovo ? opt.vcf_denovo_carriers : 0;
   if (dnf_k > 0 || dnc_k > 0) eval.set_vcf_denovo_detail(dnf_k, dnc_k);
   const int B = std::max(1, opt.batch);
@@ -452,7 +453,8 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     }
     S.min = Rs->af;
     S.calls = C;
-    // DQ: biallelic SNV records of an autosome (evals[2] > 0: the engine ran the de novo model) at or above the threshold
+    // DQ: biallelic SNV records of an autosome, and of chrX under --vcf_denovo_chrX (evals[2] > 0: the engine ran the de
+    // novo model), at or above the threshold
     S.has_dq = opt.vcf_denovo && !r.indel && Rs->evals[2] > 0 && Rs->denovo_lr >= opt.denovo_llr;
     S.dq = Rs->denovo_lr;
     return S;
