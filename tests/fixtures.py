@@ -9,6 +9,7 @@ import os
 import numpy as np
 
 import polymutt_amd as pm
+from parity import nonfinite
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYNTH = os.path.join(ROOT, "tests", "golden", "synth")
@@ -33,6 +34,10 @@ FLAT_RTOL = 1e-12
 
 def make_dataset(name, directory):
     c = CASES[name]
+    if "hard" in c:   # GLFs of tests/hard_sites.py: sites the generator never makes
+        import hard_sites
+        hard_sites.write_case(directory, c["shape"], c["families"], c["sites"], c["seed"], c["hard"])
+        return c
     pm.synth_write_dataset(directory, c["shape"], c["families"], c["sites"], c["seed"])
     if "pos" in c:   # the --pos file the reference read
         with open(os.path.join(directory, "pos.txt"), "w") as fh:
@@ -108,6 +113,13 @@ def compare_to_dump(res, dump, label=""):
     Integer fields exact; log10-likelihoods to LLK_RTOL; minimisers to FREQ_ATOL except where the
     objective is flat to rounding (then the likelihoods must still agree); emission exact."""
     problems = []
+
+    def finite_or_same(name, e, o):   # (tests/parity.py: no tolerance test below is True for a NaN)
+        bad = nonfinite(e, o)
+        if bad.any():
+            i = int(np.argmax(bad))
+            problems.append(f"{label}{name}: {int(bad.sum())} non-finite values, first {e[i]!r} vs reference {o[i]!r}")
+
     n = len(dump["status"])
     assert len(res) == n, (len(res), n)
     st = dump["status"]
@@ -134,23 +146,27 @@ def compare_to_dump(res, dump, label=""):
         if not m.any():
             continue
         e, o = res["varllk"][m, k], dump["varllk"][m, k]
-        rel = np.abs(e - o) / np.maximum(np.abs(o), 1e-300)
+        finite_or_same(f"varllk[{k}]", e, o)
+        with np.errstate(invalid="ignore"):
+            rel = np.abs(e - o) / np.maximum(np.abs(o), 1e-300)
         if (rel > LLK_RTOL).any():
-            i = int(np.argmax(rel))
+            i = int(np.nanargmax(rel))
             problems.append(f"{label}varllk[{k}] rel err {rel[i]:.3g} ({e[i]!r} vs reference {o[i]!r})")
         if k > 0:   # see tests/parity.py: divergences on flat objectives are allowed, no others
-            d = np.abs(res["varfreq"][m, k] - dump["varfreq"][m, k]) > FREQ_ATOL
+            finite_or_same(f"varfreq[{k}]", res["varfreq"][m, k], dump["varfreq"][m, k])
+            with np.errstate(invalid="ignore"):
+                d = np.abs(res["varfreq"][m, k] - dump["varfreq"][m, k]) > FREQ_ATOL
             flat += int((d & (rel <= FLAT_RTOL)).sum())
             nonflat += int((d & (rel > FLAT_RTOL)).sum())
             runs += int(m.sum())
     if nonflat:
         problems.append(f"{label}{nonflat} minimiser divergences on non-flat objectives in {runs} Brent runs")
-    d = np.abs(res["var_post_prob"][called] - dump["var_post_prob"][called])
-    if d.size and d.max() > 1e-9:
-        problems.append(f"{label}var_post_prob max abs err {d.max():.3g}")
-    d = np.abs(res["poly_qual"][called] - dump["poly_qual"][called])
-    if d.size and d.max() > 1e-6:
-        problems.append(f"{label}poly_qual max abs err {d.max():.3g}")
+    for f, tol in (("var_post_prob", 1e-9), ("poly_qual", 1e-6)):
+        finite_or_same(f, res[f][called], dump[f][called])
+        with np.errstate(invalid="ignore"):
+            d = np.abs(res[f][called] - dump[f][called])
+        if (d > tol).any():
+            problems.append(f"{label}{f} max abs err {np.nanmax(d):.3g}")
     # the harness flags every site that reaches OutputVCF(_denovo); emit==2 is a de novo record that
     # OutputVCF_denovo itself suppresses (denovoLR < minLLR)
     emitted = (res["emit"] != 0).astype(np.int32)
@@ -158,9 +174,12 @@ def compare_to_dump(res, dump, label=""):
         i = int(np.nonzero(emitted != dump["emitted"])[0][0])
         problems.append(f"{label}emitted differs at {int((emitted != dump['emitted']).sum())} sites, first {i}")
     em = dump["emitted"] == 1
-    d = np.abs(res["denovo_lr"][em] - dump["denovo_lr"][em])
-    if d.size and d.max() > 1e-6 * max(1.0, np.abs(dump["denovo_lr"][em]).max()):
-        problems.append(f"{label}denovo_lr max abs err {d.max():.3g}")
+    finite_or_same("denovo_lr", res["denovo_lr"][em], dump["denovo_lr"][em])
+    with np.errstate(invalid="ignore"):
+        d = np.abs(res["denovo_lr"][em] - dump["denovo_lr"][em])
+        ref_lr = dump["denovo_lr"][em][np.isfinite(dump["denovo_lr"][em])]
+    if (d > 1e-6 * max(1.0, np.abs(ref_lr).max() if ref_lr.size else 0.0)).any():
+        problems.append(f"{label}denovo_lr max abs err {np.nanmax(d):.3g}")
     # The harness counts calls of the virtual Brent objective f(); the engine and oracle also count the
     # direct likelihood evaluations that bypass it (de novo mono, the lone-nuclear-family eval at 0.5),
     # so a reference count of 0 matches 0 or 1.

@@ -9,7 +9,8 @@ its usual tolerances and asserts pm_engine_brent_variants() == the recipe's vari
 loop: the recipes' variants are exactly the parsed table, each named by one recipe.
 
 Workloads vary the kernel, not the data: every site comes from the synthetic generator (shape "+dn": a planted de novo
-child, so --denovo runs reach cfg-7 items).  An oracle result depends on neither the geometry, the switches nor the
+child, so --denovo runs reach cfg-7 items); tests/test_gpu_hard_sites.py runs a subset of these recipes on the sites the
+generator never makes (tests/hard_sites.py).  An oracle result depends on neither the geometry, the switches nor the
 numerics and is computed once per (workload, --denovo, class).
 
 Family counts (plan_units deals families to lanes family-major and round-robin, so slot row 1 fills once n_fam > T):

@@ -36,7 +36,7 @@ def test_engine_matches_reference_dump(built, tmp_path, name, numerics):
     eng.begin_section(chrom)
     if ora:
         ora.begin_section(chrom)
-    res, calls = [], []
+    res, ores, calls = [], [], []
     counts = {"oracle eval_path_mismatch": 0, "oracle flat_divergence": 0}
     for s in range(0, len(ref), 128):   # several batches: results must not depend on batching
         e, ec = eng.run(pl[s:s + 128], dm[s:s + 128], ref[s:s + 128])
@@ -45,13 +45,32 @@ def test_engine_matches_reference_dump(built, tmp_path, name, numerics):
             st = compare_results(e, o, ec, oc, label=f"{name}[{s}] ")
             counts["oracle eval_path_mismatch"] += st["eval_path_mismatch"]
             counts["oracle flat_divergence"] += st["flat_divergence"]
+            ores.append(o)
         res.append(e)
     import numpy as np
     res = np.concatenate(res)
-    st = compare_to_dump(res, golden_dump(name), label=name + " ")
+    dump = golden_dump(name)
+    st = compare_to_dump(res, dump, label=name + " ")
     counts["dump eval_path_mismatch"] = st["eval_path_mismatch"]
     counts["dump flat_divergence"] = st["flat_divergence"]
-    if numerics == pm.NUM_EXACT:   # identical Brent evaluation counts (and so minimisers) in exact mode
+    if numerics == pm.NUM_EXACT and "hard" in case:
+        # tests/hard_sites.py builds configurations whose two alleles no read supports (a site nobody has data for, the
+        # ref + alt configurations of a `nonref` site): their objective is flat, the last bit of the cross-family sum
+        # decides Brent's path, and the evaluation counts need not match (compare_results and
+        # compare_to_dump have checked that the likelihoods at both minimisers agree).  Which configurations those are
+        # is read off the bytes; every other one keeps the exact-mode rule: the oracle's and the reference's counts
+        # and minimisers.
+        import hard_sites
+        from fixtures import FREQ_ATOL
+        ores = np.concatenate(ores)
+        called = dump["status"] == 0
+        rule = called[:, None] & (np.arange(7)[None, :] < dump["n_cfg"][:, None]) & ~hard_sites.flat_configs(pl, ref)
+        assert rule[:, 1:].any(axis=0).all(), "every configuration is minimised on objectives that are not flat"
+        for what, evals, freq in (("oracle", ores["evals"], ores["varfreq"]), ("reference", dump["evals"], dump["varfreq"])):
+            same = (res["evals"] == evals) | ((evals == 0) & (res["evals"] == 1))   # (see compare_to_dump)
+            assert same[rule].all(), (name, what, np.argwhere(rule & ~same)[:8].tolist())
+            assert (np.abs(res["varfreq"] - freq)[rule] <= FREQ_ATOL).all(), (name, what)
+    elif numerics == pm.NUM_EXACT:   # identical Brent evaluation counts (and so minimisers) in exact mode
         assert not any(counts.values()), (name, counts)
     if ora:
         assert (eng.counters().as_array() == ora.counters().as_array()).all(), (name, counts)

@@ -27,6 +27,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))   # hard_sites
 OUT = os.path.join(ROOT, "tests", "golden", "synth")
 PM_REF = os.path.join(ROOT, "oracle", "_ref", "pm_ref")
 
@@ -88,6 +89,23 @@ CASES = {
     "multi_chr2process_one": ("quad+multi", 20, 200, 149, ["--chr2process", "2"], {"cli_only": True}),
 }
 
+# Sites the generator never makes (tests/hard_sites.py): the pedigree files come from the generator, the GLFs from
+# hard_block(pedigree, sites, seed, classes) through hard_sites.write_glf_dataset.  "filters": the flags are the
+# thresholds hard_sites.filter_params reads off the block.  `badref` is in none of them (a GLF record cannot hold it).
+_NUC = {"hard": {"classes": ["tv", "missing", "nonref", "triallelic", "dense", "real", "highaf", "mendel", "stats"]}}
+_EXT = {"hard": {"classes": ["tv", "missing", "nonref", "triallelic", "dense", "highaf", "mendel", "stats"]}}
+CASES.update({
+    "hard_quad": ("quad", 12, 120, 211, [], _NUC),
+    "hard_trio": ("trio", 12, 120, 223, [], _NUC),
+    "hard_mixed": ("mixed", 13, 120, 227, [], _NUC),
+    "hard_extmix": ("extmix", 5, 117, 229, [], _EXT),
+    "hard_quad_denovo": ("quad", 12, 120, 233, ["--denovo", "--rate_denovo", "1e-5"], _NUC),
+    "hard_extmix_denovo": ("extmix", 5, 117, 239, ["--denovo", "--rate_denovo", "1e-5"], _EXT),
+    "hard_quad_chrX": ("quad", 12, 120, 241, ["--chrX", "1"], _NUC),
+    "hard_quad_quick": ("quad", 12, 120, 251, ["--quick_call"], _NUC),
+    "hard_quad_filters": ("quad", 12, 120, 257, [], {"hard": dict(_NUC["hard"], filters=True)}),
+})
+
 SITE_DUMP = np.dtype([("pos", "<i4"), ("ref", "<i4"), ("status", "<i4"), ("total_depth", "<i4"),
                       ("num_samp_with_data", "<i4"), ("avg_map_qual", "<f8"), ("perc_samp_with_data", "<f8"),
                       ("n_cfg", "<i4"), ("maxidx", "<i4"), ("var_post_prob", "<f8"), ("poly_qual", "<f8"),
@@ -120,7 +138,13 @@ def make_case(name):
     extras = CASES[name][5] if len(CASES[name]) > 5 else {}
     tmp = tempfile.mkdtemp(prefix="pm_gold_")
     try:
-        pm.synth_write_dataset(tmp, shape, nfam, nsites, seed)
+        if "hard" in extras:
+            import hard_sites
+            block = hard_sites.write_case(tmp, shape, nfam, nsites, seed, extras["hard"])
+            if extras["hard"].get("filters"):
+                flags = hard_sites.filter_flags(hard_sites.filter_params(block)[0])
+        else:
+            pm.synth_write_dataset(tmp, shape, nfam, nsites, seed)
         if "pos" in extras:
             with open(os.path.join(tmp, "pos.txt"), "w") as fh:
                 fh.write("".join(f"{l} {p}\n" for l, p in extras["pos"]))
