@@ -374,8 +374,8 @@ int pm_engine_set_vcf_denovo(pm_engine *eng, int32_t on);
  * planes g11, g12, g22 are read.  A de novo Brent that hits ITMAX is a stuck site like any other.  FP64, a fixed
  * reduction order and no floating-point atomics: the same input gives the same bytes.
  * Not in the model: chrY and MT sections (no DQ, as before); pseudo-autosomal regions (ignored, as in the standard chrX
- * model); the per-family and per-child detail, which stays autosomal only -- pm_engine_vcf_denovo_rows keeps returning 0
- * rows on chrX sections.
+ * model); the per-family and per-child detail, which stays autosomal only by default -- pm_engine_vcf_denovo_rows keeps
+ * returning 0 rows on chrX sections unless pm_engine_set_vcf_denovo_chrx_detail below is on.
  * on = 0 (the default): nothing is allocated or launched, every output byte is that of an engine without the feature.
  * It may be set at any point between batches.  PM_EINVAL: an engine without vcf_mode, pm_engine_set_vcf_denovo not on, or a
  * submitted batch not yet collected.  pm_engine_set_vcf_denovo(eng, 0) switches this off too (and so does a repeated
@@ -414,7 +414,8 @@ int pm_engine_set_vcf_denovo_chrx(pm_engine *eng, int32_t on);
 int pm_engine_set_vcf_denovo_detail(pm_engine *eng, int32_t fam_k, int32_t car_k, int32_t want_all);
 
 /* The rows of the last finished batch (after pm_engine_run, _run_vcf, _collect, or _run_device + _sync): *n_rows, and
- * their batch indices in site[n_rows] (may be NULL).  0 rows with the feature off and on chrX/Y/MT sections.  After
+ * their batch indices in site[n_rows] (may be NULL).  0 rows with the feature off and on chrX/Y/MT sections (on chrX:
+ * unless pm_engine_set_vcf_denovo_chrx_detail is on).  After
  * PM_EBRENT only the rows before the stuck site are counted and valid.  Like the two readers below, PM_EINVAL while a
  * submitted batch has not been collected. */
 int pm_engine_vcf_denovo_rows(pm_engine *eng, int32_t *n_rows, int32_t *site);
@@ -426,6 +427,43 @@ int pm_engine_vcf_denovo_families(pm_engine *eng, pm_fam_lr *top, double *sum, d
 /* top[n_rows][car_k] (entries past the non-founder count are {-1, -1, -1, -1, 0, 0.0}) and all[n_rows][n_person]
  * (person = p; may be NULL; PM_EINVAL when asked for without want_all).  PM_EINVAL with car_k == 0. */
 int pm_engine_vcf_denovo_carriers(pm_engine *eng, pm_person_dn *top, pm_person_dn *all);
+
+/* The families and the children behind each DQ of a chrX section: pm_engine_set_vcf_denovo_detail's outputs in the
+ * sex-aware model of pm_engine_set_vcf_denovo_chrx (additive to ABI 8: callers detect the feature by this symbol; no
+ * reference counterpart).  An opt-in of its own: with pm_engine_set_vcf_denovo_chrx and pm_engine_set_vcf_denovo_detail
+ * both on and this switch off, chrX sections keep giving 0 rows.  Everything is in the three states and the four tables
+ * T_F, T_M, Tdn_F = T_F M3, Tdn_M = T_M H3 of pm_engine_set_vcf_denovo_chrx, with its founder priors ((f, 0, 1 - f) for a
+ * male, Hardy-Weinberg for everyone else) and its routing (every family with offspring is peeled).  x_N = varfreq[2],
+ * x_D = varfreq[1].
+ *   Rows: the called sites (status == 0) of a PM_CHR_X section with evals[2] > 0 and denovo_lr >= pm_params.denovo_min_llr,
+ *     in ascending site order within the batch.
+ *   Per family f:  D_f = log10 L_f^dn(x_N) - log10 L_f^std(x_D), L_f the family's factor of the chrX de novo objective and
+ *     of the standard chrX objective: a family with offspring by the peel (Tdn of the child's sex at x_N, the
+ *     FamilyLikelihoodES.cpp:1391 quirk included; plain T of the child's sex everywhere at x_D); a founders-only family
+ *     the product of its persons in person order, a male l11 x + l22 (1 - x), everyone else the Hardy-Weinberg quadratic.
+ *     Each log10 is taken of the whole double.  Sum_f D_f = denovo_lr up to summation rounding.
+ *   Per non-founder c with both parents in its family (father fa, mother mo), at x_N in the de novo model:
+ *     pp    = Sum_{a in {0, 2}, b in {0, 1, 2}} J_c(a, b, NonMendX(a, b, sex_c)) / L_f^dn, capped at 1, the sum in (a, b)
+ *             order.  J_c(a, b, S) = L_f^dn restricted to G_fa = a, G_mo = b, G_c in S.  NonMendX(a, b, sex) = the states s
+ *             allowed for that sex -- 0, 1, 2 for a daughter or a child of unknown sex, 0 and 2 for a son -- with
+ *             T_sex[a][b][s] = 0.  A father has no state 1: those three pairs contribute exactly 0.  A son of a
+ *             heterozygous mother has an empty set: that pair contributes 0 too.
+ *     event = the pair (a, b) of the largest term, then the state of its set with the largest J_c(a, b, {s}); ties go to
+ *             the first pair in (a, b) order, then to the first state; (-1, -1, -1) when every term is 0.
+ *     Genotypes are reported as the GLF indices g[s] in pm_person_dn: a hemizygous male's state 0 or 2 is reported as g11
+ *     or g22.  Founders get (-1, -1, -1) and 0.0.  A child reached only through a type-3 step with a marriage partial
+ *     has pp = 0 (plain T there), as on autosomes.
+ * Rankings, padding entries and determinism are those of pm_engine_set_vcf_denovo_detail (k_vdn_rows as it is, then
+ * k_vdn_who_x, one block per row at a time; fixed reduction trees, no floating-point atomics: the same input gives the
+ * same bytes).  The outputs go to that feature's buffers with its fam_k, car_k and want_all, so pm_engine_vcf_denovo_rows,
+ * _families and _carriers read them unchanged.  The site results and the genotype rows of chrX sections are those of
+ * pm_engine_set_vcf_denovo_chrx alone, byte for byte; autosomal sections, chrY and MT are untouched.
+ * on = 0 (the default) frees what this switch allocated: nothing is allocated or launched.
+ * PM_EINVAL: an engine without vcf_mode, a submitted batch not yet collected, pm_engine_set_vcf_denovo_chrx not on, or
+ * pm_engine_set_vcf_denovo_detail off (fam_k = car_k = 0).  Any later call of pm_engine_set_vcf_denovo,
+ * pm_engine_set_vcf_denovo_chrx or pm_engine_set_vcf_denovo_detail switches this off, because each rebuilds what it rests
+ * on: set this switch last. */
+int pm_engine_set_vcf_denovo_chrx_detail(pm_engine *eng, int32_t on);
 
 /* Page-locked host memory for pm_engine_submit's inputs and the result rows (H2D/D2H at full PCIe rate). */
 int pm_host_alloc(uint64_t bytes, void **h_ptr);

@@ -151,6 +151,12 @@ struct pm_engine {
   int2* d_vw_kids = nullptr;
   int8_t* d_vw_is_kid = nullptr;
   double* d_vw_jbuf = nullptr;                                          // [vw_grid][vw_n_es * 13]
+  // the same on chrX (pm_engine_set_vcf_denovo_chrx_detail): off = no buffer, no launch; the outputs are the detail's own
+  bool vwx_on = false;
+  int vwx_grid = 0, vwx_n_kids = 0;
+  int2* d_vwx_kids = nullptr;                                           // every person with both parents in the family
+  int8_t* d_vwx_is_kid = nullptr;
+  double* d_vwx_jbuf = nullptr;                                         // [vwx_grid][vwx_n_kids * 13]
   std::vector<int> fam_kind_h, fam_perm_h;
   std::vector<int32_t> fa_h, mo_h;  // family-local parent indices (-1: none)
   unsigned long long* d_counters = nullptr;
@@ -374,7 +380,7 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf,
                   E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws, E->d_vdnx_terms, E->d_vdnx_ws, E->d_vw_row_site, E->d_vw_pfam, E->d_vw_fam_top, E->d_vw_fam_sum,
                   E->d_vw_fam_all, E->d_vw_fam_line, E->d_vw_car_top, E->d_vw_car_all, E->d_vw_car_line, E->d_vw_kids, E->d_vw_is_kid,
-                  E->d_vw_jbuf};
+                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf};
   for (void* b : bufs) if (b) hipFree(b);
   for (auto& pl : E->d_jit_slots)
     for (int* b : pl) if (b) hipFree(b);
@@ -1148,7 +1154,8 @@ static int launch_vcf_denovo(pm_engine* E, const DevArgs& A) {
 }
 
 // The same on a chrX section (pm_engine_set_vcf_denovo_chrx): k_vdn_brent_x on its own terms and workspace, then
-// k_finalize_vdn as it is.  No detail rows on X: counts[10] stays 0.
+// k_finalize_vdn as it is.  No detail rows on X (counts[10] stays 0) unless pm_engine_set_vcf_denovo_chrx_detail is on:
+// then k_vdn_rows as it is and k_vdn_who_x into the detail's buffers.
 static int launch_vcf_denovo_x(pm_engine* E, const DevArgs& A) {
   VdnXArgs V;
   V.terms = E->d_vdnx_terms; V.n_terms = E->vdnx_terms; V.n_peel = E->vdnx_peel; V.ws = E->d_vdnx_ws;
@@ -1160,6 +1167,19 @@ static int launch_vcf_denovo_x(pm_engine* E, const DevArgs& A) {
   if (int rc = mark(E, E->brent_events, false)) return rc;
   hipLaunchKernelGGL(k_finalize_vdn, dim3((A.n + 255) / 256), dim3(256), 0, E->stream, A);
   HIP_TRY(hipGetLastError());
+  if (E->vwx_on) {
+    VdnWhoArgs W;
+    W.fam_k = E->vw_fam_k; W.car_k = E->vw_car_k; W.row_site = E->d_vw_row_site;
+    W.fam_top = E->d_vw_fam_top; W.fam_sum = E->d_vw_fam_sum; W.fam_all = E->d_vw_fam_all; W.fam_line = E->d_vw_fam_line;
+    W.pfam = E->d_vw_pfam; W.car_top = E->d_vw_car_top; W.car_all = E->d_vw_car_all; W.car_line = E->d_vw_car_line;
+    W.kids = E->d_vwx_kids; W.n_nuc = 0; W.n_es = E->vwx_n_kids; W.is_kid = E->d_vwx_is_kid; W.jbuf = E->d_vwx_jbuf;
+    hipLaunchKernelGGL(k_vdn_rows, dim3(1), dim3(1024), 0, E->stream, A, E->d_vw_row_site);
+    HIP_TRY(hipGetLastError());
+    // (vwx_grid <= vdnx_grid, the blocks of k_vdn_brent_x's workspace, and <= vw_grid, the blocks of the detail's lines)
+    const int wgrid = std::max(1, std::min(E->vwx_grid, A.n));
+    hipLaunchKernelGGL(E->vdnx_T == 64 ? k_vdn_who_x<64> : k_vdn_who_x<256>, dim3(wgrid), dim3(E->vdnx_T), 0, E->stream, A, V, W);
+    HIP_TRY(hipGetLastError());
+  }
   return PM_OK;
 }
 
@@ -1391,8 +1411,17 @@ static void vw_free(pm_engine* E) {
   for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
 }
 
-// pm_engine_set_vcf_denovo_chrx's buffers (the stream is idle)
+// pm_engine_set_vcf_denovo_chrx_detail's buffers (the stream is idle)
+static void vwx_free(pm_engine* E) {
+  E->vwx_on = false;
+  E->vwx_grid = E->vwx_n_kids = 0;
+  void** bufs[] = {(void**)&E->d_vwx_kids, (void**)&E->d_vwx_is_kid, (void**)&E->d_vwx_jbuf};
+  for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+}
+
+// pm_engine_set_vcf_denovo_chrx's buffers (the stream is idle), and the chrX detail that rests on them
 static void vdnx_free(pm_engine* E) {
+  vwx_free(E);
   E->vdnx_on = false;
   if (E->d_vdnx_terms) (void)hipFree(E->d_vdnx_terms);
   if (E->d_vdnx_ws) (void)hipFree(E->d_vdnx_ws);
@@ -1526,6 +1555,7 @@ int pm_engine_set_vcf_denovo_detail(pm_engine* E, int32_t fam_k, int32_t car_k, 
   }
   HIP_TRY(hipSetDevice(E->device));
   HIP_TRY(hipStreamSynchronize(E->stream));
+  vwx_free(E);   // (it writes into the buffers rebuilt here)
   vw_free(E);
   if (fam_k == 0 && car_k == 0) return PM_OK;
   // the children: every person with both parents in the family, of the closed-form nuclear families (k_vdn_brent's
@@ -1573,6 +1603,53 @@ int pm_engine_set_vcf_denovo_detail(pm_engine* E, int32_t fam_k, int32_t car_k, 
   HIP_TRY(hipMemcpy(E->d_vw_is_kid, is_kid.data(), np, hipMemcpyHostToDevice));
   E->vw_grid = grid; E->vw_n_nuc = n_nuc; E->vw_n_es = n_es;
   E->vw_fam_k = fam_k; E->vw_car_k = car_k;
+  return PM_OK;
+}
+
+int pm_engine_set_vcf_denovo_chrx_detail(pm_engine* E, int32_t on) {
+  if (!E) { pm_set_last_error("pm_engine_set_vcf_denovo_chrx_detail: invalid arguments"); return PM_EINVAL; }
+  if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_denovo_chrx_detail: the engine was created without vcf_mode"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_vcf_denovo_chrx_detail: a submitted batch has not been collected"); return PM_EINVAL; }
+  if (!E->vdnx_on) {
+    pm_set_last_error("pm_engine_set_vcf_denovo_chrx_detail: needs pm_engine_set_vcf_denovo_chrx(engine, 1) first (vcf_denovo_chrx is off)");
+    return PM_EINVAL;
+  }
+  if (E->vw_fam_k == 0 && E->vw_car_k == 0) {
+    pm_set_last_error("pm_engine_set_vcf_denovo_chrx_detail: needs pm_engine_set_vcf_denovo_detail first (vcf_denovo_detail is off)");
+    return PM_EINVAL;
+  }
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  vwx_free(E);
+  if (!on) return PM_OK;
+  // the children: every person with both parents in the family, of every family with offspring (all peeled on X:
+  // k_vdn_brent_x's routing, so the autosomal list's closed-form group does not apply)
+  const size_t np = (size_t)E->n_person;
+  std::vector<int2> kids;
+  std::vector<int8_t> is_kid(np, 0);
+  for (int f = 0; f < E->n_fam; f++) {
+    const int p0 = E->fam_start_h[f], n = E->fam_start_h[f + 1] - p0;
+    if (E->fam_kind_h[f] == PM_FAM_FOUNDERS) continue;
+    for (int j = 0; j < n; j++) {
+      const int fa = E->fa_h[p0 + j], mo = E->mo_h[p0 + j];
+      if (fa < 0 || mo < 0 || fa >= n || mo >= n || fa == mo) continue;
+      kids.push_back(make_int2(f, j));
+      is_kid[p0 + j] = 1;
+    }
+  }
+  // one block per row at a time on k_vdn_brent_x's workspace (vdnx_grid blocks) and the detail's per-block lines (vw_grid
+  // blocks); the children's term buffer caps the grid at 256 MiB
+  int grid = std::min(E->vdnx_grid, E->vw_grid);
+  const size_t per_block = kids.size() * 13 * sizeof(double);
+  if (per_block) grid = (int)std::max<size_t>(1, std::min<size_t>(grid, ((size_t)1 << 28) / per_block));
+  int rc;
+  if ((rc = dalloc(&E->d_vwx_kids, kids.size())) || (rc = dalloc(&E->d_vwx_is_kid, np)) ||
+      (per_block && E->vw_car_k > 0 && (rc = dalloc(&E->d_vwx_jbuf, (size_t)grid * kids.size() * 13))))
+    { vwx_free(E); return rc; }
+  if (!kids.empty()) HIP_TRY(hipMemcpy(E->d_vwx_kids, kids.data(), sizeof(int2) * kids.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(E->d_vwx_is_kid, is_kid.data(), np, hipMemcpyHostToDevice));
+  E->vwx_grid = grid; E->vwx_n_kids = (int)kids.size();
+  E->vwx_on = true;
   return PM_OK;
 }
 

@@ -285,8 +285,11 @@ struct VdnXArgs {
 
 // d_es_lk<3> on chrX with the transmission tables passed in (LDS), picked by the sex of the step's child: t[0] to a
 // daughter (or a child of unknown sex), t[27] to a son.  tdn where the de novo model mutates, tpl (plain) elsewhere.
+// CL: d_es_lk3_vdn<CL>'s clamps (k_vdn_who_x); without CL nothing is added.
+template <bool CL = false>
 __device__ __forceinline__ double d_es_lk3_vdn_x(const DevArgs& A, int f, const uint8_t* pl, const double* lk, const int* gidx, double freq,
-                                                 const double* tdn, const double* tpl, double* ws, size_t st) {
+                                                 const double* tdn, const double* tpl, double* ws, size_t st, int c0 = -1, int m0 = 0,
+                                                 int c1 = -1, int m1 = 0, int c2 = -1, int m2 = 0) {
   const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0, nf = A.fam_founders[f];
 #define PP(i, j) ws[((size_t)(i) * 3 + (j)) * st]
 #define MPP(sl, x, y) ws[((size_t)n * 3 + (size_t)(sl) * 9 + (x) * 3 + (y)) * st]
@@ -301,7 +304,9 @@ __device__ __forceinline__ double d_es_lk3_vdn_x(const DevArgs& A, int f, const 
     }
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-      const double pen = lk[R[gidx[j] * np]];
+      double pen = lk[R[gidx[j] * np]];
+      if (CL)
+        if ((i == c0 && !((m0 >> j) & 1)) || (i == c1 && !((m1 >> j) & 1)) || (i == c2 && !((m2 >> j) & 1))) pen = 0.0;
       PP(i, j) = fo ? pr[j] * pen : pen;
     }
   }
@@ -805,6 +810,242 @@ __global__ void __launch_bounds__(T) k_vdn_who(DevArgs A, VdnArgs V, VdnWhoArgs 
         for (int w = 1; w < NW; w++)
           if (fam_lr_before(s_red[par][w], s_redf[par][w], bl, bf)) { bl = s_red[par][w]; bf = s_redf[par][w]; }
         par ^= 1;
+        if (threadIdx.x == 0) {
+          pm_person_dn o;
+          o.person = -1; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
+          if (bf != INT_MAX) o = line[bf];
+          W.car_top[(size_t)row * W.car_k + k] = o;
+        }
+        if (bf == INT_MAX) { prev_pp = -INFINITY; prev_p = INT_MAX; }   // exhausted: every later round is empty too
+        else { prev_pp = bl; prev_p = bf; }
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same on chrX (pm_engine_set_vcf_denovo_chrx_detail): the families and the children behind each DQ of a PM_CHR_X
+// section, in the sex-aware model of k_vdn_brent_x.
+
+// NonMendX(a, b, sex): the states a child of that sex can carry (a son 0 and 2, anyone else all three) that the plain
+// transmission from parents in states (a, b) gives probability 0, as a 3-bit mask.  tpl: [0..26] to a daughter, [27..53]
+// to a son.  Empty for a son of a heterozygous mother.
+__device__ __forceinline__ int vdnx_nonmend(const double* tpl, int k, bool male) {
+  const double* t = tpl + (male ? 27 : 0) + k * 3;
+  int m = 0;
+#pragma unroll
+  for (int s = 0; s < 3; s++)
+    if (!(male && s == 1) && t[s] == 0.0) m |= 1 << s;
+  return m;
+}
+
+// one round of k_vdn_who's ranking: the block's best (value, index) by fam_lr_before, the same fixed tree
+template <int T>
+__device__ __forceinline__ void vdnx_best(double& bl, int& bf, double (*red)[4], int (*redf)[4], int& par) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ol = __shfl_xor(bl, o, 64);
+    const int of = __shfl_xor(bf, o, 64);
+    if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
+  }
+  if ((threadIdx.x & 63) == 0) { red[par][threadIdx.x >> 6] = bl; redf[par][threadIdx.x >> 6] = bf; }
+  __syncthreads();
+  bl = red[par][0]; bf = redf[par][0];
+#pragma unroll
+  for (int w = 1; w < T / 64; w++)
+    if (fam_lr_before(red[par][w], redf[par][w], bl, bf)) { bl = red[par][w]; bf = redf[par][w]; }
+  par ^= 1;
+}
+
+// k_vdn_who_x: per row of a chrX section, in the three states of the record's (ref, alt) and the model of k_vdn_brent_x,
+//   D_f = log10 L_f^dn(varfreq[2]) - log10 L_f^std(varfreq[1]) of every family (k_vdn_brent_x's factors, pass 1 and pass 0),
+//   pp_c = Sum_{a in {0,2}, b} J_c(a, b, NonMendX(a, b, sex_c)) / L_f^dn and the event of every non-founder c,
+// and their top-k rankings.  One block of T threads per row at a time, after k_finalize_vdn on the engine's stream (the
+// peel workspace is k_vdn_brent_x's).  Families: the terms round robin over the threads.  Children (W.kids: every one is
+// peeled, there is no closed form on X; W.n_nuc is 0): k_vdn_who's stages A, B and C with barriers between them.  A father
+// has no state 1, so stage A deals out six items per child, not nine, and writes the other three as exact zeros; a son of
+// a heterozygous mother has no non-Mendelian state, that pair gives 0 without a peel.
+// Sums and rankings are k_vdn_who's fixed trees: no atomics.
+template <int T>
+__global__ void __launch_bounds__(T) k_vdn_who_x(DevArgs A, VdnXArgs V, VdnWhoArgs W) {
+  constexpr int NW = T / 64;
+  __shared__ double s_lk[256];
+  __shared__ double s_tpl[54], s_tdn[54], s_m3[9], s_h3[9];   // [0..26] to a daughter, [27..53] to a son
+  __shared__ double s_red[2][4];
+  __shared__ int s_redf[2][4];
+  for (int i = threadIdx.x; i < 256; i += T) s_lk[i] = A.lktab[i];
+  if (threadIdx.x < 54) s_tpl[threadIdx.x] = c_TBA[1 + threadIdx.x / 27][threadIdx.x % 27];
+  const int rows = A.counts[10], nf = A.n_fam, nk = W.n_es;
+  const size_t np = (size_t)A.n_person;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  double* ws = V.ws + (size_t)blockIdx.x * A.ws_per_lane * T + threadIdx.x;
+  double* jb = W.jbuf + (size_t)blockIdx.x * nk * 13;
+  int par = 0;
+  for (int row = blockIdx.x; row < rows; row += gridDim.x) {   // (block-uniform: every thread reaches the barriers)
+    const int site = W.row_site[row];
+    const pm_site_result* R = A.res + site;
+    const int r = A.ref[site];
+    const int a1 = r & 15, a2 = r >> 4;
+    const int gidx[3] = {d_gi(a1, a1), d_gi(a1, a2), d_gi(a2, a2)};
+    const uint8_t* pl = A.pl + (size_t)site * np * 10;
+    const double xN = R->varfreq[2], xD = R->varfreq[1];
+    __syncthreads();   // (the previous row no longer reads the tables, the lines or jbuf; s_tpl is written)
+    if (threadIdx.x < 9) {
+      const int x = threadIdx.x / 3, y = threadIdx.x % 3;
+      s_m3[threadIdx.x] = A.M[vdn_pick3(gidx, x) * 10 + vdn_pick3(gidx, y)];
+      s_h3[threadIdx.x] = (x == 1 || y == 1) ? 0.0 : V.a4[(((x ? a2 : a1) - 1) & 3) * 4 + (((y ? a2 : a1) - 1) & 3)];   // (bases are 1..4)
+    }
+    __syncthreads();
+    if (threadIdx.x < 54) {
+      const int ij = (threadIdx.x % 27) / 3, k = threadIdx.x % 3;
+      const double* tp = s_tpl + (threadIdx.x < 27 ? 0 : 27);
+      const double* mm = threadIdx.x < 27 ? s_m3 : s_h3;
+      double s = 0.0;
+      for (int m = 0; m < 3; m++) s += tp[ij * 3 + m] * mm[m * 3 + k];
+      s_tdn[threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (W.fam_k > 0) {
+      double* line = W.fam_all ? W.fam_all + (size_t)row * nf : W.fam_line + (size_t)blockIdx.x * nf;
+      double part = 0.0;
+      for (int q = threadIdx.x; q < V.n_terms; q += T) {
+        const int x = V.terms[q];
+        int f = x;
+        double l_dn, l_std;
+        if (q < V.n_peel) {
+          l_dn = log10(d_es_lk3_vdn_x(A, f, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, T));
+          l_std = log10(d_es_lk3_vdn_x(A, f, pl, s_lk, gidx, xD, s_tpl, s_tpl, ws, T));
+        } else {   // founders only: the family's first person carries the product over its persons, in person order
+          f = W.pfam[x];
+          const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0;
+          if (x != p0) continue;
+          double mN = 1.0, mD = 1.0;
+          int eN = 0, eD = 0;
+          const double gN = 1 - xN, gD = 1 - xD;
+          for (int j = 0; j < n; j++) {
+            const uint8_t* P = pl + p0 + j;
+            const double l11 = s_lk[P[gidx[0] * np]], l12 = s_lk[P[gidx[1] * np]], l22 = s_lk[P[gidx[2] * np]];
+            const bool male = A.sex[p0 + j] == MALE;   // lkSinglePerson: a male is hemizygous
+            int e1;
+            mN = frexp(mN * (male ? l11 * xN + l22 * gN : l11 * (xN * xN) + l12 * (2 * xN * gN) + l22 * (gN * gN)), &e1);
+            eN += e1;
+            mD = frexp(mD * (male ? l11 * xD + l22 * gD : l11 * (xD * xD) + l12 * (2 * xD * gD) + l22 * (gD * gD)), &e1);
+            eD += e1;
+          }
+          l_dn = vdn_log10_me(mN, eN);
+          l_std = vdn_log10_me(mD, eD);
+        }
+        const double D = l_dn - l_std;
+        line[f] = D;
+        part += D;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+      if (lane == 0) s_red[par][wv] = part;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        double s = s_red[par][0];
+#pragma unroll
+        for (int w = 1; w < NW; w++) s += s_red[par][w];
+        W.fam_sum[row] = s;
+      }
+      par ^= 1;
+      double prev_lr = 0.0;
+      int prev_f = -1;
+      for (int k = 0; k < W.fam_k; k++) {   // round k takes the best entry that comes after round k - 1's in the order
+        double bl = 0.0;
+        int bf = INT_MAX;
+        for (int q = threadIdx.x; q < V.n_terms; q += T) {
+          const int x = V.terms[q];
+          int f = x;
+          if (q >= V.n_peel) {
+            f = W.pfam[x];
+            if (x != A.fam_start[f]) continue;
+          }
+          const double d = line[f];   // (written by this thread above)
+          const bool after = k == 0 ? d == d : (d < prev_lr || (d == prev_lr && f > prev_f));
+          if (after && fam_lr_before(d, f, bl, bf)) { bl = d; bf = f; }
+        }
+        vdnx_best<T>(bl, bf, s_red, s_redf, par);
+        if (threadIdx.x == 0) {
+          pm_fam_lr o;
+          o.fam = bf == INT_MAX ? -1 : bf; o.pad = 0; o.lr = bf == INT_MAX ? 0.0 : bl;
+          W.fam_top[(size_t)row * W.fam_k + k] = o;
+        }
+        if (bf == INT_MAX) { prev_lr = -INFINITY; prev_f = INT_MAX; }   // exhausted: every later round is empty too
+        else { prev_lr = bl; prev_f = bf; }
+      }
+    }
+    if (W.car_k > 0) {
+      pm_person_dn* line = W.car_all ? W.car_all + (size_t)row * np : W.car_line + (size_t)blockIdx.x * np;
+      for (int p = threadIdx.x; p < (int)np; p += T)   // founders (and anyone without both parents): no value
+        if (!W.is_kid[p]) {
+          pm_person_dn o;
+          o.person = p; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
+          line[p] = o;
+        }
+      if (nk > 0) {   // (block-uniform)
+        for (int it = threadIdx.x; it < nk * 6; it += T) {   // stage A: the six pairs of a father in state 0 or 2
+          const int ci = it / 6, b = it % 3, k = (it % 6 < 3 ? 0 : 6) + b;
+          const int2 kd = W.kids[ci];
+          const int p0 = A.fam_start[kd.x], jc = kd.y, fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
+          const int nonm = vdnx_nonmend(s_tpl, k, A.sex[p0 + jc] == MALE);
+          double J = 0.0;
+          if (nonm)
+            J = d_es_lk3_vdn_x<true>(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, T, fa, 1 << (k / 3), mo, 1 << b, jc, nonm);
+          jb[ci * 9 + k] = J;
+          if (k < 3) jb[ci * 9 + 3 + b] = 0.0;   // a father has no state 1: exactly 0, no peel
+        }
+        __syncthreads();
+        double* jb2 = jb + (size_t)nk * 9;
+        for (int it = threadIdx.x; it < nk * 4; it += T) {   // stage B
+          const int ci = it / 4, slot = it % 4;
+          const int2 kd = W.kids[ci];
+          const int p0 = A.fam_start[kd.x], jc = kd.y, fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
+          double v = -1.0;
+          if (slot == 3) v = d_es_lk3_vdn_x(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, T);
+          else {
+            double bj = 0.0;
+            int bi = -1;
+            for (int q = 0; q < 9; q++) { const double J = jb[ci * 9 + q]; if (J > bj) { bj = J; bi = q; } }
+            if (bi >= 0 && ((vdnx_nonmend(s_tpl, bi, A.sex[p0 + jc] == MALE) >> slot) & 1))
+              v = d_es_lk3_vdn_x<true>(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, T, fa, 1 << (bi / 3), mo, 1 << (bi % 3), jc, 1 << slot);
+          }
+          jb2[it] = v;
+        }
+        __syncthreads();
+        for (int ci = threadIdx.x; ci < nk; ci += T) {   // stage C
+          const int2 kd = W.kids[ci];
+          const int p = A.fam_start[kd.x] + kd.y;
+          double num = 0.0, bj = 0.0;
+          int bi = -1;
+          for (int q = 0; q < 9; q++) { const double J = jb[ci * 9 + q]; num += J; if (J > bj) { bj = J; bi = q; } }
+          const double L = jb2[ci * 4 + 3];
+          double bv = 0.0;
+          int bs = -1;
+          for (int s = 0; s < 3; s++) { const double v = jb2[ci * 4 + s]; if (v > bv) { bv = v; bs = s; } }
+          pm_person_dn o;
+          o.person = p; o.pad = 0;
+          o.fa_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bi / 3)); o.mo_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bi % 3));
+          o.kid_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bs));
+          o.pp = L > 0.0 ? fmin(num / L, 1.0) : 0.0;   // (L_f and the terms come from separate peels: rounding may pass 1)
+          line[p] = o;
+        }
+      }
+      __syncthreads();   // the row's entries are visible to the block: the ranking reads what other threads wrote
+      double prev_pp = 0.0;
+      int prev_p = -1;
+      for (int k = 0; k < W.car_k; k++) {
+        double bl = 0.0;
+        int bf = INT_MAX;
+        for (int i = threadIdx.x; i < nk; i += T) {
+          const int2 kd = W.kids[i];
+          const int p = A.fam_start[kd.x] + kd.y;
+          const double d = line[p].pp;
+          const bool after = k == 0 ? d == d : (d < prev_pp || (d == prev_pp && p > prev_p));
+          if (after && fam_lr_before(d, p, bl, bf)) { bl = d; bf = p; }
+        }
+        vdnx_best<T>(bl, bf, s_red, s_redf, par);
         if (threadIdx.x == 0) {
           pm_person_dn o;
           o.person = -1; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;

@@ -128,6 +128,7 @@ EXPORTS = {
     "pm_engine_denovo_carriers": (i32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_engine_set_vcf_denovo": (i32, [C.c_void_p, i32]),
     "pm_engine_set_vcf_denovo_chrx": (i32, [C.c_void_p, i32]),
+    "pm_engine_set_vcf_denovo_chrx_detail": (i32, [C.c_void_p, i32]),
     "pm_engine_set_vcf_denovo_detail": (i32, [C.c_void_p, i32, i32, i32]),
     "pm_engine_vcf_denovo_rows": (i32, [C.c_void_p, P(i32), C.c_void_p]),
     "pm_engine_vcf_denovo_families": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -432,8 +433,16 @@ class Engine:
         """pm_engine_set_vcf_denovo_chrx (after set_vcf_denovo(True)): batches run on a PM_CHR_X section get N, its
         maximiser, its evaluation count and DQ from the sex-aware three-state chrX model (hemizygous males, the
         transmission picked by the child's sex); off (the default) leaves every output byte as it was.
-        Any later set_vcf_denovo call switches it off again.  The per-family / per-child detail stays autosomal only."""
+        Any later set_vcf_denovo call switches it off again.  The per-family / per-child detail stays autosomal only
+        unless set_vcf_denovo_chrx_detail is on."""
         self._check(self.lib.pm_engine_set_vcf_denovo_chrx(self.h, 1 if on else 0))
+
+    def set_vcf_denovo_chrx_detail(self, on=True):
+        """pm_engine_set_vcf_denovo_chrx_detail (after set_vcf_denovo_chrx(True) and set_vcf_denovo_detail): the rows of
+        a PM_CHR_X section -- called sites whose DQ is at or above denovo_min_llr -- get their families and children from
+        the sex-aware model, read by vcf_denovo_rows / _families / _carriers with the detail's fam_k, car_k and want_all.
+        Set it last: any later set_vcf_denovo, set_vcf_denovo_chrx or set_vcf_denovo_detail call switches it off."""
+        self._check(self.lib.pm_engine_set_vcf_denovo_chrx_detail(self.h, 1 if on else 0))
 
     def set_vcf_denovo_detail(self, fam_k, car_k, want_all=False):
         """pm_engine_set_vcf_denovo_detail (after set_vcf_denovo(True)): per row -- a called autosomal site whose DQ is at

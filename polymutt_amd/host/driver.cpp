@@ -51,6 +51,7 @@ Options parse_command_line(int argc, char** argv) {
       {"denovo_families", 'i', &o.denovo_families}, {"denovo_carriers", 'i', &o.denovo_carriers},
       {"vcf_denovo", 'b', &o.vcf_denovo}, {"vcf_denovo_families", 'i', &o.vcf_denovo_families},
       {"vcf_denovo_carriers", 'i', &o.vcf_denovo_carriers}, {"vcf_denovo_chrX", 'b', &o.vcf_denovo_chrX},
+      {"vcf_denovo_chrX_detail", 'b', &o.vcf_denovo_chrX_detail},
   };
   auto assign = [](Flag& f, const char* v) {
     switch (f.kind) {
@@ -111,6 +112,11 @@ Options parse_command_line(int argc, char** argv) {
   if (o.vcf_denovo_carriers_given) {
     if (!o.vcf_denovo) throw FatalError("--vcf_denovo_carriers needs --vcf_denovo\n");
     if (o.vcf_denovo_carriers < 1 || o.vcf_denovo_carriers > 8) throw FatalError("--vcf_denovo_carriers takes a person count from 1 to 8\n");
+  }
+  if (o.vcf_denovo_chrX_detail) {
+    if (!o.vcf_denovo_chrX) throw FatalError("--vcf_denovo_chrX_detail needs --vcf_denovo_chrX\n");
+    if (!o.vcf_denovo_families_given && !o.vcf_denovo_carriers_given)
+      throw FatalError("--vcf_denovo_chrX_detail needs --vcf_denovo_families and / or --vcf_denovo_carriers\n");
   }
   if (o.denovo_carriers_given) {
     if (!o.denovo) throw FatalError("--denovo_carriers needs --denovo\n");

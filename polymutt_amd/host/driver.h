@@ -41,8 +41,12 @@ struct Options {
   int vcf_denovo_families = 0, vcf_denovo_carriers = 0;
   bool vcf_denovo_families_given = false, vcf_denovo_carriers_given = false;
   // --vcf_denovo_chrX (with --vcf_denovo): biallelic SNV records of the --chrX chromosome get ;DQ= too, from the sex-aware
-  // three-state chrX model (pm_engine_set_vcf_denovo_chrx); DQ alone: the DNF / DNC detail stays autosomal only
+  // three-state chrX model (pm_engine_set_vcf_denovo_chrx); DQ alone: the DNF / DNC detail stays autosomal only ...
   bool vcf_denovo_chrX = false;
+  // ... unless --vcf_denovo_chrX_detail (with --vcf_denovo_chrX and --vcf_denovo_families and / or --vcf_denovo_carriers):
+  // chrX SNV records that get ;DQ= get those tags too, from the same model (pm_engine_set_vcf_denovo_chrx_detail); in DNCE
+  // a male's genotype is printed as its single allele, as the GT column prints him
+  bool vcf_denovo_chrX_detail = false;
   std::string cmd;
   pm_params params() const;
 };
@@ -98,6 +102,9 @@ class SiteEvaluator {
   virtual void set_vcf_denovo(bool on) { (void)on; throw FatalError("--vcf_denovo is not supported by this evaluator\n"); }
   // --vcf_denovo_chrX: once, after set_vcf_denovo(true) and before the first batch (pm_engine_set_vcf_denovo_chrx)
   virtual void set_vcf_denovo_chrx(bool on) { (void)on; throw FatalError("--vcf_denovo_chrX is not supported by this evaluator\n"); }
+  // --vcf_denovo_chrX_detail: once, after set_vcf_denovo_chrx(true) and set_vcf_denovo_detail and before the first batch
+  // (pm_engine_set_vcf_denovo_chrx_detail); vcf_denovo_rows and the two readers then serve chrX batches too
+  virtual void set_vcf_denovo_chrx_detail(bool on) { (void)on; throw FatalError("--vcf_denovo_chrX_detail is not supported by this evaluator\n"); }
   // --vcf_denovo_families / --vcf_denovo_carriers: set_vcf_denovo_detail once, after set_vcf_denovo(true) and before the
   // first batch; then, for the batch the last run_vcf() returned (also after it threw a BrentError: the rows before the
   // stuck site), vcf_denovo_rows returns the row count and writes the rows' batch indices to site (may be null), and the

@@ -125,6 +125,9 @@ class EngineEvaluator : public SiteEvaluator {
   void set_vcf_denovo_detail(int fam_k, int car_k) override {
     for (auto* e : eng_) check(pm_engine_set_vcf_denovo_detail(e, fam_k, car_k, 0));
   }
+  void set_vcf_denovo_chrx_detail(bool on) override {
+    for (auto* e : eng_) check(pm_engine_set_vcf_denovo_chrx_detail(e, on ? 1 : 0));
+  }
   int vcf_denovo_rows(int32_t* site) override {   // (the engine that ran the batch last returned)
     if (!last_) throw FatalError("GPU engine error: no finished batch\n");
     int32_t n = 0;

@@ -236,6 +236,7 @@ struct Pending {          // one record awaiting output, in file order
   int slot = -1;
   int a1 = 0, a2 = 0;
   bool indel = false;
+  bool chrx = false;      // a record of the --chrX chromosome (DNCE prints a male's genotype as its single allele)
   int dp_idx = -1;        // DP's FORMAT index as it stood when the record was read: the reference writes each record at
                           // once (PedVCF.cpp:118-160), with DP looked up per record until found (:311-314)
   // classify_pre (parallel): the record's own facts; classify_apply (serial, in file order) the FORMAT state machine
@@ -377,6 +378,8 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   if (opt.vcf_denovo && opt.vcf_denovo_chrX) eval.set_vcf_denovo_chrx(true);
   const int dnf_k = opt.vcf_denovo ? opt.vcf_denovo_families : 0, dnc_k = opt.vcf_denovo ? opt.vcf_denovo_carriers : 0;
   if (dnf_k > 0 || dnc_k > 0) eval.set_vcf_denovo_detail(dnf_k, dnc_k);
+  if (opt.vcf_denovo && opt.vcf_denovo_chrX && opt.vcf_denovo_chrX_detail && (dnf_k > 0 || dnc_k > 0))
+    eval.set_vcf_denovo_chrx_detail(true);   // (last: the other three setters switch it off)
   const int B = std::max(1, opt.batch);
   // Two batches: the main thread reads, classifies and parses records into one while the flusher thread runs the
   // engine on the other, formats its records and hands their text to the writer thread.  A batch's PL rows are in
@@ -529,14 +532,16 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       }
       if (S.dnc) {   // ;DNC=<pid>[,...];DNCP=<%.4g>[,...];DNCE=<fa>x<mo>><kid>[,...]
         static const char* g2[10] = {"AA", "AC", "AG", "AT", "CC", "CG", "CT", "GG", "GT", "TT"};
-        auto gs = [&](int g) { return (g >= 0 && g < 10) ? g2[g] : ".."; };
+        static const char* g1[10] = {"A", "AC", "AG", "AT", "C", "CG", "CT", "G", "GT", "T"};   // hemizygous: one allele
+        auto gs = [&](int g, bool hap = false) { return (g >= 0 && g < 10) ? (hap ? g1[g] : g2[g]) : ".."; };
         std::string ids, pps, evs;
         for (int k = 0; k < dnc_k && S.dnc[k].person >= 0 && S.dnc[k].person < np; k++) {
           snprintf(v, sizeof(v), "%.4g", S.dnc[k].pp);
           if (k) { ids += ','; pps += ','; evs += ','; }
           ids += ped.column_pid[S.dnc[k].person];
           pps += v;
-          evs += gs(S.dnc[k].fa_g); evs += 'x'; evs += gs(S.dnc[k].mo_g); evs += '>'; evs += gs(S.dnc[k].kid_g);
+          evs += gs(S.dnc[k].fa_g, r.chrx); evs += 'x'; evs += gs(S.dnc[k].mo_g); evs += '>';
+          evs += gs(S.dnc[k].kid_g, r.chrx && ped.sex[S.dnc[k].person] == 1);
         }
         if (!ids.empty()) { dq_t += ";DNC="; dq_t += ids; dq_t += ";DNCP="; dq_t += pps; dq_t += ";DNCE="; dq_t += evs; }
       }
@@ -910,6 +915,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       // chromosome class of the record (PedVCF.cpp:121-124)
       const std::string chrom = L.substr(r.cols[0].b, r.cols[0].e - r.cols[0].b);
       const int cls = chrom == opt.chrX ? PM_CHR_X : chrom == opt.chrY ? PM_CHR_Y : chrom == opt.MT ? PM_CHR_MT : PM_CHR_AUTO;
+      r.chrx = cls == PM_CHR_X;
       if (withdata[k] == 0) {   // written with the previous record's QUAL / AF / genotypes (:113)
         if (lead && !computed_any) {   // ... which an earlier rank computed: written after the exchange
           fprintf(lead, "%d\t%s\n", r.dp_idx, r.line.c_str());   // (with its DP index snapshot)
