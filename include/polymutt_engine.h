@@ -465,6 +465,33 @@ int pm_engine_vcf_denovo_carriers(pm_engine *eng, pm_person_dn *top, pm_person_d
  * on: set this switch last. */
 int pm_engine_set_vcf_denovo_chrx_detail(pm_engine *eng, int32_t on);
 
+/* Genotype posteriors of every person of every written record of a vcf_mode batch (additive to ABI 8: callers detect
+ * the feature by this symbol; FamilyLikelihoodSeq_VCF::OutputVCF prints GT and GQ only, so there is no reference
+ * counterpart for the output, only for the values).  One row entry is the vector post[] from which the engine takes
+ * a person's best genotype and GQ -- P(g11), P(g12), P(g22) given the whole pedigree at the site's frequency
+ * (pm_site_result.af), with the founder priors and the single-family prior mode of the genotype rows -- each value
+ * rounded once from double to float.  The chromosome class keeps its rules: hemizygous persons (chrX / chrY males,
+ * everyone on MT) have p[1] = 0, chrY females are all zero, and a person whose normalising sum is zero is all zero.
+ * DS = p[1] + 2 p[2]. */
+typedef struct {
+  float p[3];                  /* P(g11), P(g12), P(g22) given the pedigree */
+} pm_vcf_post;
+
+/* Switch the posterior plane on or off (off at creation).  With it on, every batch runs one extra pass after the
+ * standard posterior stage (k_vcf_post_lean / k_vcf_post_nuc / k_vcf_post_es, chosen as that stage's kernels are),
+ * which writes only the plane: the site results and the genotype rows are those of the engine without it, byte for
+ * byte.  The device buffer is max_batch x n_person x 12 bytes, allocated on the first `on` and freed on `off` or
+ * pm_engine_destroy; off = nothing allocated, nothing launched.  Independent of the pm_engine_set_vcf_denovo family:
+ * either may be on without the other and neither switches the other off.  It may be set at any point between
+ * batches.  PM_EINVAL: an engine without vcf_mode, or a submitted batch not yet collected. */
+int pm_engine_set_vcf_posteriors(pm_engine *eng, int32_t on);
+
+/* The plane of the last finished batch (pm_engine_run, pm_engine_run_vcf or pm_engine_submit / pm_engine_collect):
+ * *n_rows = the batch's row count, out[row * n_person + person] with the rows of pm_site_result.call_row and the
+ * persons in pm_pedigree order.  out may be NULL (the count alone).  After PM_EBRENT: the same prefix of rows the
+ * batch returned.  PM_EINVAL: the feature is off, or a submitted batch has not been collected. */
+int pm_engine_vcf_posteriors(pm_engine *eng, int32_t *n_rows, pm_vcf_post *out);
+
 /* Page-locked host memory for pm_engine_submit's inputs and the result rows (H2D/D2H at full PCIe rate). */
 int pm_host_alloc(uint64_t bytes, void **h_ptr);
 int pm_host_free(void *h_ptr);

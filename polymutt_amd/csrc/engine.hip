@@ -6,6 +6,7 @@
 #include "brent_plan.h"
 #include "brent_variants.h"
 #include "vcf_denovo_dev.h"
+#include "vcf_post_dev.h"
 
 #define PM_BRENT_X(part, ...) extern template __global__ void k_brent<__VA_ARGS__>(DevArgs, int);
 PM_BRENT_VARIANTS
@@ -157,6 +158,9 @@ struct pm_engine {
   int2* d_vwx_kids = nullptr;                                           // every person with both parents in the family
   int8_t* d_vwx_is_kid = nullptr;
   double* d_vwx_jbuf = nullptr;                                         // [vwx_grid][vwx_n_kids * 13]
+  // the genotype posterior plane of vcf_mode batches (pm_engine_set_vcf_posteriors): off = no buffer, no launch
+  bool vp_on = false, vp_valid = false;   // vp_valid: the last finished batch filled the plane
+  pm_vcf_post* d_vp = nullptr;            // [max_batch][n_person]
   std::vector<int> fam_kind_h, fam_perm_h;
   std::vector<int32_t> fa_h, mo_h;  // family-local parent indices (-1: none)
   unsigned long long* d_counters = nullptr;
@@ -380,7 +384,7 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf,
                   E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws, E->d_vdnx_terms, E->d_vdnx_ws, E->d_vw_row_site, E->d_vw_pfam, E->d_vw_fam_top, E->d_vw_fam_sum,
                   E->d_vw_fam_all, E->d_vw_fam_line, E->d_vw_car_top, E->d_vw_car_all, E->d_vw_car_line, E->d_vw_kids, E->d_vw_is_kid,
-                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf};
+                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf, E->d_vp};
   for (void* b : bufs) if (b) hipFree(b);
   for (auto& pl : E->d_jit_slots)
     for (int* b : pl) if (b) hipFree(b);
@@ -1183,6 +1187,30 @@ static int launch_vcf_denovo_x(pm_engine* E, const DevArgs& A) {
   return PM_OK;
 }
 
+// The posterior plane of a vcf_mode batch's rows (vcf_post_dev.h): one more pass behind the standard posterior stage, with
+// that stage's choice of kernels (lean: k_posterior_lean ran; es: the section has peeled families) and launch shapes.
+static int launch_vcf_posteriors(pm_engine* E, const DevArgs& A, bool lean, bool es) {
+  VpArgs P;
+  P.post = E->d_vp;
+  if (lean) hipLaunchKernelGGL(k_vcf_post_lean, dim3(E->grid_post), dim3(256), (size_t)E->n_fam * 4, E->stream, A, P);
+  else hipLaunchKernelGGL(k_vcf_post_nuc, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
+  HIP_TRY(hipGetLastError());
+  if (es && A.n_es_pers > 0) {   // k_posterior_es's choice between the LDS and the HBM workspace
+    const size_t per = (size_t)E->ws_per_lane * sizeof(double);
+    int bt = 0;
+    for (int t : {256, 128, 64})
+      if (!bt && per * t <= 64 * 1024 && !E->sw.es_post_hbm) bt = t;
+    if (bt) {
+      const int per_cu = std::max(1, (int)((160 * 1024) / (per * bt + 3 * 1024)));
+      hipLaunchKernelGGL(k_vcf_post_es<true>, dim3(E->n_cu * per_cu * 2), dim3(bt), per * bt, E->stream, A, P);
+    } else
+      hipLaunchKernelGGL(k_vcf_post_es<false>, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
+    HIP_TRY(hipGetLastError());
+  }
+  E->vp_valid = true;
+  return PM_OK;
+}
+
 static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* dm, const uint8_t* ref, pm_site_result* res,
                         pm_geno_call* calls) {
   DevArgs A = make_args(E, n, pl, dm, ref, res, calls);
@@ -1287,6 +1315,10 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
         hipLaunchKernelGGL(pe, dim3(E->n_cu * per_cu * 2), dim3(bt), per * bt, E->stream, A);
       } else
         hipLaunchKernelGGL(E->par.denovo ? k_posterior_es<true> : k_posterior_es<false>, dim3(E->grid_post), dim3(256), 0, E->stream, A);
+    }
+    if (E->vp_on) {
+      HIP_TRY(hipGetLastError());
+      if ((rc = launch_vcf_posteriors(E, A, lean, es))) return rc;
     }
   }
   HIP_TRY(hipGetLastError());
@@ -1477,6 +1509,40 @@ int pm_engine_set_vcf_denovo(pm_engine* E, int32_t on) {
     return rc;
   HIP_TRY(hipMemcpy(E->d_vdn_terms, terms.data(), sizeof(int) * terms.size(), hipMemcpyHostToDevice));
   E->vdn_on = true;
+  return PM_OK;
+}
+
+int pm_engine_set_vcf_posteriors(pm_engine* E, int32_t on) {
+  if (!E) { pm_set_last_error("pm_engine_set_vcf_posteriors: invalid arguments"); return PM_EINVAL; }
+  if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_posteriors: the engine was created without vcf_mode"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_vcf_posteriors: a submitted batch has not been collected"); return PM_EINVAL; }
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  if (!on) {
+    E->vp_on = E->vp_valid = false;
+    if (E->d_vp) (void)hipFree(E->d_vp);
+    E->d_vp = nullptr;
+    return PM_OK;
+  }
+  if (E->vp_on) return PM_OK;   // (already on: the last batch's plane stays)
+  const size_t cells = (size_t)E->max_batch * E->n_person;   // max_batch x n_person x 12 bytes
+  if (int rc = dalloc(&E->d_vp, cells)) return rc;
+  HIP_TRY(hipMemset(E->d_vp, 0, cells * sizeof(pm_vcf_post)));
+  E->vp_on = true;
+  E->vp_valid = false;   // (no batch has filled it yet)
+  return PM_OK;
+}
+
+int pm_engine_vcf_posteriors(pm_engine* E, int32_t* n_rows, pm_vcf_post* out) {
+  if (!E || !n_rows) { pm_set_last_error("pm_engine_vcf_posteriors: invalid arguments"); return PM_EINVAL; }
+  if (!E->vp_on) { pm_set_last_error("pm_engine_vcf_posteriors: the feature is off (pm_engine_set_vcf_posteriors)"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_vcf_posteriors: a submitted batch has not been collected"); return PM_EINVAL; }
+  *n_rows = E->vp_valid ? E->last_rows : 0;
+  if (out && *n_rows > 0) {
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipMemcpy(out, E->d_vp, sizeof(pm_vcf_post) * (size_t)*n_rows * E->n_person, hipMemcpyDeviceToHost));
+  }
   return PM_OK;
 }
 

@@ -2963,9 +2963,16 @@ __device__ __forceinline__ void lean_fam_bytes(const uint8_t* pl, int np, int p0
 // operation order -- the same values bit for bit
 // NF = the family's persons when the caller knows them for the whole wave (3: trio, 4: quad; 0 = runtime n): the
 // kid loops and the one-kid / two-kid selects then resolve at compile time (same operations, same bits)
-template <bool VCF, int NF = 0>
+// POST (pm_engine_set_vcf_posteriors' extra pass, vcf_post_dev.h): the three quotients of every person go to vp as
+// floats instead of a genotype row entry; the other instantiations compile as before
+__device__ __forceinline__ void d_store_post(pm_vcf_post* dst, double s, double a, double b, double c) {
+  pm_vcf_post v;   // (one 12-byte store per person; s: the normalising sum, 0 = no posterior)
+  v.p[0] = s != 0 ? (float)(a / s) : 0.f; v.p[1] = s != 0 ? (float)(b / s) : 0.f; v.p[2] = s != 0 ? (float)(c / s) : 0.f;
+  *dst = v;
+}
+template <bool VCF, int NF = 0, bool POST = false>
 __device__ __forceinline__ void lean_nuc_post(const DevArgs& A, const double* s_lk, const double* s_gq, const uint32_t* by,
-                                              size_t out, int p0, int n_rt, const double* pp) {
+                                              size_t out, int p0, int n_rt, const double* pp, pm_vcf_post* vp = nullptr) {
   const int n = NF ? NF : n_rt;
   double lF[3], lM[3], kl[2][3];
 #pragma unroll
@@ -2996,6 +3003,7 @@ __device__ __forceinline__ void lean_nuc_post(const DevArgs& A, const double* s_
     if (j == 0) { q11 = m[0] + m[1] + m[2]; q12 = m[3] + m[4] + m[5]; q22 = m[6] + m[7] + m[8]; }
     else { q11 = m[0] + m[3] + m[6]; q12 = m[1] + m[4] + m[7]; q22 = m[2] + m[5] + m[8]; }
     const double sum = q11 + q12 + q22;
+    if constexpr (POST) { d_store_post(vp + out + p0 + j, sum, q11, q12, q22); continue; }
     if constexpr (VCF) {   // one quotient: post[best]
       const int best = d_best3(q11, q12, q22);
       const double qb = best == 0 ? q11 : best == 1 ? q12 : q22;
@@ -3039,6 +3047,7 @@ __device__ __forceinline__ void lean_nuc_post(const DevArgs& A, const double* s_
       if (!z22) { const double v = (two ? q22 * lo : q22) * w; g[2] = h[2] ? g[2] + v : v; h[2] = true; }
     }
     const double sum = g[0] + g[1] + g[2];
+    if constexpr (POST) { d_store_post(vp + out + p0 + j, sum, g[0], g[1], g[2]); continue; }
     if constexpr (VCF) {
       // d_best3 over the quotients g[t] / sum (sum > 0, g >= 0: division is monotone) is the first t whose
       // quotient equals the largest one, post[b] with b = d_best3(g); an earlier quotient can only equal it

@@ -103,6 +103,8 @@ FAM_LR_DTYPE = np.dtype([("fam", "<i4"), ("pad", "<i4"), ("lr", "<f8")])   # pm_
 assert FAM_LR_DTYPE.itemsize == 16
 PERSON_DN_DTYPE = np.dtype([("person", "<i4"), ("fa_g", "i1"), ("mo_g", "i1"), ("kid_g", "i1"), ("pad", "i1"), ("pp", "<f8")])   # pm_person_dn
 assert PERSON_DN_DTYPE.itemsize == 16
+VCF_POST_DTYPE = np.dtype([("p", "<f4", (3,))])   # pm_vcf_post
+assert VCF_POST_DTYPE.itemsize == 12
 
 _lib = None
 
@@ -133,6 +135,8 @@ EXPORTS = {
     "pm_engine_vcf_denovo_rows": (i32, [C.c_void_p, P(i32), C.c_void_p]),
     "pm_engine_vcf_denovo_families": (i32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_engine_vcf_denovo_carriers": (i32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pm_engine_set_vcf_posteriors": (i32, [C.c_void_p, i32]),
+    "pm_engine_vcf_posteriors": (i32, [C.c_void_p, P(i32), C.c_void_p]),
     "pm_host_alloc": (i32, [u64, P(C.c_void_p)]),
     "pm_host_free": (i32, [C.c_void_p]),
     "pm_engine_to_planar": (i32, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
@@ -484,6 +488,22 @@ class Engine:
         full = np.zeros((rows, self.n_person), dtype=PERSON_DN_DTYPE) if self._vw_all else None
         self._check(self.lib.pm_engine_vcf_denovo_carriers(self.h, _ptr(top), None if full is None else _ptr(full)))
         return top, full
+
+    def set_vcf_posteriors(self, on=True):
+        """pm_engine_set_vcf_posteriors (vcf_mode engines): every batch also keeps, for every person of every written
+        row, the posterior vector behind the row's best genotype and GQ; off (the default) allocates and launches
+        nothing.  The site results and the genotype rows are the same bytes either way."""
+        self._check(self.lib.pm_engine_set_vcf_posteriors(self.h, 1 if on else 0))
+
+    def vcf_posteriors(self):
+        """pm_engine_vcf_posteriors for the last finished batch: float32 [rows, n_person, 3] = P(g11), P(g12), P(g22)
+        given the pedigree, rows indexed by call_row (after a stuck Brent: the rows the batch returned)."""
+        n = i32(0)
+        self._check(self.lib.pm_engine_vcf_posteriors(self.h, C.byref(n), None))
+        post = np.zeros((n.value, self.n_person), dtype=VCF_POST_DTYPE)
+        if n.value:
+            self._check(self.lib.pm_engine_vcf_posteriors(self.h, C.byref(n), _ptr(post)))
+        return post["p"].copy() if n.value else np.zeros((0, self.n_person, 3), dtype=np.float32)
 
     def stuck_site(self):
         """pm_engine_stuck_site: the first site of the last finished batch whose Brent hit ITMAX (-1: none)."""

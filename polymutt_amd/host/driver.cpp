@@ -51,7 +51,7 @@ Options parse_command_line(int argc, char** argv) {
       {"denovo_families", 'i', &o.denovo_families}, {"denovo_carriers", 'i', &o.denovo_carriers},
       {"vcf_denovo", 'b', &o.vcf_denovo}, {"vcf_denovo_families", 'i', &o.vcf_denovo_families},
       {"vcf_denovo_carriers", 'i', &o.vcf_denovo_carriers}, {"vcf_denovo_chrX", 'b', &o.vcf_denovo_chrX},
-      {"vcf_denovo_chrX_detail", 'b', &o.vcf_denovo_chrX_detail},
+      {"vcf_denovo_chrX_detail", 'b', &o.vcf_denovo_chrX_detail}, {"vcf_posteriors", 'b', &o.vcf_posteriors},
   };
   auto assign = [](Flag& f, const char* v) {
     switch (f.kind) {
@@ -104,6 +104,7 @@ Options parse_command_line(int argc, char** argv) {
     if (o.denovo_families < 1 || o.denovo_families > 8) throw FatalError("--denovo_families takes a family count from 1 to 8\n");
   }
   if (o.vcf_denovo && o.vcfInFile.empty()) throw FatalError("--vcf_denovo needs --in_vcf\n");
+  if (o.vcf_posteriors && o.vcfInFile.empty()) throw FatalError("--vcf_posteriors needs --in_vcf\n");
   if (o.vcf_denovo_chrX && !o.vcf_denovo) throw FatalError("--vcf_denovo_chrX needs --vcf_denovo\n");
   if (o.vcf_denovo_families_given) {
     if (!o.vcf_denovo) throw FatalError("--vcf_denovo_families needs --vcf_denovo\n");

@@ -47,6 +47,10 @@ struct Options {
   // chrX SNV records that get ;DQ= get those tags too, from the same model (pm_engine_set_vcf_denovo_chrx_detail); in DNCE
   // a male's genotype is printed as its single allele, as the GT column prints him
   bool vcf_denovo_chrX_detail = false;
+  // --vcf_posteriors (with --in_vcf): every sample of every written record also gets DS and GP, the dosage and the three
+  // genotype posteriors given the pedigree behind its GT and GQ (pm_engine_set_vcf_posteriors); combines freely with the
+  // --vcf_denovo flags
+  bool vcf_posteriors = false;
   std::string cmd;
   pm_params params() const;
 };
@@ -119,6 +123,11 @@ class SiteEvaluator {
   }
   virtual void vcf_denovo_families(pm_fam_lr* top) { (void)top; throw FatalError("--vcf_denovo_families is not supported by this evaluator\n"); }
   virtual void vcf_denovo_carriers(pm_person_dn* top) { (void)top; throw FatalError("--vcf_denovo_carriers is not supported by this evaluator\n"); }
+  // --vcf_posteriors: set_vcf_posteriors once, before the first batch; then, for the batch the last run_vcf() returned
+  // (also after it threw a BrentError: the rows it returned), vcf_posteriors writes the plane [rows][n_person] to out and
+  // returns the row count (pm_engine_set_vcf_posteriors / pm_engine_vcf_posteriors)
+  virtual void set_vcf_posteriors(bool on) { (void)on; throw FatalError("--vcf_posteriors is not supported by this evaluator\n"); }
+  virtual int vcf_posteriors(pm_vcf_post* out) { (void)out; throw FatalError("--vcf_posteriors is not supported by this evaluator\n"); }
   // Host memory for the batch buffers (the engine: page-locked, for asynchronous copies)
   virtual void* host_alloc(size_t bytes);
   virtual void host_free(void* p);

@@ -142,6 +142,15 @@ class EngineEvaluator : public SiteEvaluator {
     if (!last_) throw FatalError("GPU engine error: no finished batch\n");
     check(pm_engine_vcf_denovo_carriers(last_, top, nullptr));
   }
+  void set_vcf_posteriors(bool on) override {
+    for (auto* e : eng_) check(pm_engine_set_vcf_posteriors(e, on ? 1 : 0));
+  }
+  int vcf_posteriors(pm_vcf_post* out) override {   // (the engine that ran the batch last returned)
+    if (!last_) throw FatalError("GPU engine error: no finished batch\n");
+    int32_t n = 0;
+    check(pm_engine_vcf_posteriors(last_, &n, out));
+    return n;
+  }
   void* host_alloc(size_t bytes) override {
     void* p = nullptr;
     if (pm_host_alloc(bytes ? bytes : 1, &p) != PM_OK || !p) return SiteEvaluator::host_alloc(bytes);   // pageable fallback

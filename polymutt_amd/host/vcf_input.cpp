@@ -251,6 +251,7 @@ struct Pending {          // one record awaiting output, in file order
 struct State {            // what FamilyLikelihoodSeq_VCF holds between records (stale output, :412-521)
   double qual = 0.0, min = 0.0;
   std::vector<pm_vcf_call> calls;    // per flattened person
+  std::vector<pm_vcf_post> post;     // --vcf_posteriors: their posteriors (all zero before the first computed record)
   int a_ref = 0;                     // allele of the label convention (always allele1 in this path)
 };
 
@@ -357,7 +358,12 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     fprintf(out, "%s",
             "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
             "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype Quality\">\n"
-            "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Read Depth\">\n"
+            "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Read Depth\">\n");
+    if (opt.vcf_posteriors)   // (--vcf_posteriors: no reference counterpart; DS as the GLF path declares it, vcf.cpp)
+      fprintf(out, "%s",
+              "##FORMAT=<ID=DS,Number=1,Type=Float,Description=\"Dosage: Defined As the Expected Alternative Allele Count\">\n"
+              "##FORMAT=<ID=GP,Number=G,Type=Float,Description=\"Genotype Posterior Probabilities Given the Pedigree\">\n");
+    fprintf(out, "%s",
             "##FORMAT=<ID=PL,Number=3,Type=Integer,Description=\"Phred-scaled Genotype Likelihoods\">\n"
             "##FORMAT=<ID=GL,Number=3,Type=Float,Description=\"Log10 Genotype Likelihoods\">\n");
     fprintf(out, "%s\n", header.c_str());
@@ -380,6 +386,8 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   if (dnf_k > 0 || dnc_k > 0) eval.set_vcf_denovo_detail(dnf_k, dnc_k);
   if (opt.vcf_denovo && opt.vcf_denovo_chrX && opt.vcf_denovo_chrX_detail && (dnf_k > 0 || dnc_k > 0))
     eval.set_vcf_denovo_chrx_detail(true);   // (last: the other three setters switch it off)
+  const bool vp = opt.vcf_posteriors;
+  if (vp) eval.set_vcf_posteriors(true);
   const int B = std::max(1, opt.batch);
   // Two batches: the main thread reads, classifies and parses records into one while the flusher thread runs the
   // engine on the other, formats its records and hands their text to the writer thread.  A batch's PL rows are in
@@ -394,13 +402,14 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     std::vector<uint8_t> ref;
     std::vector<pm_site_result> res;
     std::vector<Pending*> pend;
+    std::vector<pm_vcf_post> post;   // --vcf_posteriors: the batch's posterior plane, fetched next to the calls
     int nb = 0;
-    BatchBuf(SiteEvaluator& ev, int b, int n)
+    BatchBuf(SiteEvaluator& ev, int b, int n, bool with_post)
         : e(ev), pl((uint8_t*)ev.host_alloc((size_t)b * n * 10)), calls((pm_vcf_call*)ev.host_alloc((size_t)b * n * sizeof(pm_vcf_call))),
-          ref(b), res(b) {}
+          ref(b), res(b), post(with_post ? (size_t)b * n : 0) {}
     ~BatchBuf() { e.host_free(pl); e.host_free(calls); }
   };
-  BatchBuf bb0(eval, B, np), bb1(eval, B, np);
+  BatchBuf bb0(eval, B, np, vp), bb1(eval, B, np, vp);
   BatchBuf* const bbs[2] = {&bb0, &bb1};
   if (!bb0.pl || !bb1.pl || !bb0.calls || !bb1.calls) throw FatalError("out of host memory\n");
   int cb = 0;   // the batch the main thread fills
@@ -424,6 +433,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   FILE* lead = nullptr;   // sharded, R > 0: raw lines met before this rank's first record with data
   State st;
   st.calls.assign(np, pm_vcf_call{0, 0, PM_LBL_VCF_DIPLOID, 0});
+  if (vp) st.post.assign(np, pm_vcf_post{{0.f, 0.f, 0.f}});
 
   // The state a record is printed with: its own (a computed record) or the previous computed record's (a record
   // without data, PedVCF.cpp:113-122): QUAL, the AF minimiser and every person's call.
@@ -436,6 +446,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     double dq = 0.0;
     const pm_fam_lr* dnf = nullptr;
     const pm_person_dn* dnc = nullptr;
+    const pm_vcf_post* post = nullptr;   // --vcf_posteriors: every person's posteriors, carried like the calls
   };
   auto fresh_state = [&](const Pending& r, const pm_site_result* Rs, const pm_vcf_call* C) {
     // mono/poly -> QUAL (PedVCF.cpp:136-152), with the reference's operator-precedence slip
@@ -496,7 +507,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       fv[s] = F;
       if (F.db >= 0) totalDepth += atoi_fast(lp + F.db);
     }
-    out.resize(L.size() + 17 * ns + 1024);
+    out.resize(L.size() + (vp ? 49 : 17) * ns + 1024);   // (--vcf_posteriors: at most 32 more characters per sample)
     char* w = &out[0];
     auto put = [&](const char* p, size_t n) { memcpy(w, p, n); w += n; };
     auto fld = [&](int k) { put(lp + r.cols[k].b, (size_t)(r.cols[k].e - r.cols[k].b)); };
@@ -514,7 +525,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     int hn = snprintf(head, sizeof(head), "\t%.2f\t", S.qual);
     if (hn >= (int)sizeof(head)) { putf(hn); w += snprintf(w, (size_t)hn + 1, "\t%.2f\t", S.qual); } else putf(hn);
     fld(6);
-    const char* fmt_s = fs.PL_idx > 0 ? "GT:GQ:DP:PL" : "GT:GQ:DP:GL";
+    const char* fmt_s = vp ? (fs.PL_idx > 0 ? "GT:GQ:DP:DS:GP:PL" : "GT:GQ:DP:DS:GP:GL") : fs.PL_idx > 0 ? "GT:GQ:DP:PL" : "GT:GQ:DP:GL";
     std::string dq_t;
     if (S.has_dq) {
       char v[64];
@@ -568,6 +579,17 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       if (F.db >= 0) put(lp + F.db, (size_t)(F.de - F.db));
       else *w++ = '.';
       *w++ = ':';
+      if (vp) {   // DS:GP from the three posteriors (a hemizygous sample has two genotypes; "." without a posterior)
+        const pm_vcf_post& q = S.post[inc_cols[s].second];
+        if (c.label == PM_LBL_DOT || (q.p[0] == 0.f && q.p[1] == 0.f && q.p[2] == 0.f)) { put(".:.", 3); }
+        else {
+          put_fixed2(w, (double)q.p[1] + 2.0 * (double)q.p[2]);
+          *w++ = ':';
+          if (c.label == PM_LBL_VCF_HAPLOID) w += snprintf(w, 24, "%.3f,%.3f", (double)q.p[0], (double)q.p[2]);
+          else w += snprintf(w, 24, "%.3f,%.3f,%.3f", (double)q.p[0], (double)q.p[1], (double)q.p[2]);
+        }
+        *w++ = ':';
+      }
       if (F.pb >= 0) put(lp + F.pb, (size_t)(F.pe - F.pb));
       else *w++ = '.';
     }
@@ -577,6 +599,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   // the lead records of a shard, printed with the carried state, one at a time
   auto write_record = [&](FILE* fo, const Pending& r) {
     RecState S{st.qual, st.min, st.calls.data()};
+    S.post = st.post.data();
     std::string t;
     format_record(t, r, S);
     fwrite(t.data(), 1, t.size(), fo);
@@ -634,6 +657,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
         for (size_t k = 0; k < pend.size(); k++)
           if (pend[k]->computed && pend[k]->slot >= e.valid) { npend = k; break; }
       }
+      if (vp) eval.vcf_posteriors(bb.post.data());   // (after a stuck Brent: the rows of the records that still go out)
     }
     // the batch's rows (the sites with DQ at or above the threshold; after a stuck Brent those before it): slot -> row
     std::vector<int32_t> row_of;
@@ -654,10 +678,12 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     // the state each record prints with (sequential: a record without data takes the last computed one's)
     states.resize(npend);
     RecState cur{st.qual, st.min, st.calls.data()};
+    cur.post = st.post.data();
     for (size_t k = 0; k < npend; k++) {
       const Pending& r = *pend[k];
       if (r.computed) {
         cur = fresh_state(r, &bb.res[r.slot], calls + (size_t)bb.res[r.slot].call_row * np);
+        cur.post = vp ? bb.post.data() + (size_t)bb.res[r.slot].call_row * np : nullptr;
         const int row = (cur.has_dq && !row_of.empty()) ? row_of[r.slot] : -1;
         if (row >= 0 && dnf_k > 0) cur.dnf = dnf.data() + (size_t)row * dnf_k;
         if (row >= 0 && dnc_k > 0) cur.dnc = dnc.data() + (size_t)row * dnc_k;
@@ -683,6 +709,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     if (!pend.empty()) {   // the last state carries into the next batch
       st.qual = cur.qual; st.min = cur.min;
       if (cur.calls != st.calls.data()) std::copy(cur.calls, cur.calls + np, st.calls.begin());
+      if (vp && cur.post != st.post.data()) std::copy(cur.post, cur.post + np, st.post.begin());
     }
     {
       std::lock_guard<std::mutex> lk(free_mu);
@@ -970,10 +997,16 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
 
   // exchange: {computed any, QUAL, AF minimiser, skipped records, Brent stuck, the genotype calls} of each rank's last
   // computed record
-  const int K = 5 + np;
+  const int K = 5 + np + (vp ? 2 * np : 0);   // (--vcf_posteriors: each person's three floats in two more words)
   std::vector<int64_t> send(K), recv((size_t)N * K);
   send[0] = computed_any; send[1] = d2bits(st.qual); send[2] = d2bits(st.min); send[3] = bad_allele; send[4] = stuck;
   for (int p = 0; p < np; p++) send[5 + p] = pack_call(st.calls[p]);
+  for (int p = 0; p < np && vp; p++) {
+    uint32_t b[3];
+    memcpy(b, st.post[p].p, sizeof(b));
+    send[5 + np + 2 * p] = (int64_t)b[0] | ((int64_t)b[1] << 32);
+    send[5 + np + 2 * p + 1] = (int64_t)b[2];
+  }
   comm->allgather(send.data(), K, recv.data());
   int stuck_rank = -1;   // the first shard that met a stuck Brent: later shards' records come after it, never written
   for (int q = N - 1; q >= 0; q--)
@@ -983,12 +1016,18 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   if (lead) {   // this rank's leading no-data records, with the state of the nearest earlier rank that computed one
     State carried;
     carried.calls.assign(np, pm_vcf_call{0, 0, PM_LBL_VCF_DIPLOID, 0});
+    if (vp) carried.post.assign(np, pm_vcf_post{{0.f, 0.f, 0.f}});
     for (int q = R - 1; q >= 0; q--) {
       const int64_t* v = recv.data() + (size_t)q * K;
       if (!v[0]) continue;
       carried.qual = bits2d(v[1]);
       carried.min = bits2d(v[2]);
       for (int p = 0; p < np; p++) carried.calls[p] = unpack_call(v[5 + p]);
+      for (int p = 0; p < np && vp; p++) {
+        const uint32_t b[3] = {(uint32_t)(v[5 + np + 2 * p] & 0xFFFFFFFF), (uint32_t)((uint64_t)v[5 + np + 2 * p] >> 32),
+                               (uint32_t)(v[5 + np + 2 * p + 1] & 0xFFFFFFFF)};
+        memcpy(carried.post[p].p, b, sizeof(b));
+      }
       break;
     }
     std::swap(st, carried);
