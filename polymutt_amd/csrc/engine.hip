@@ -1129,32 +1129,51 @@ static int launch_brent(pm_engine* E, const DevArgs& A0, int list, bool unrelate
 }
 
 // The de novo Brent item of every called site of a vcf_mode batch (three-genotype mutation model, vcf_denovo_dev.h) and the
-// four result fields it fills; timed with the Brent launches (pm_kernel_stats).
-static int launch_vcf_denovo(pm_engine* E, const DevArgs& A) {
-  VdnArgs V;
-  V.terms = E->d_vdn_terms; V.n_terms = E->vdn_terms; V.n_peel = E->vdn_peel; V.n_nuc = E->vdn_nuc;
-  V.co_lds = E->vdn_lds > 0; V.co = E->d_vdn_co; V.ws = E->d_vdn_ws;
-  const int grid = std::max(1, std::min(E->vdn_grid, A.n));
+// four result fields it fills; timed with the Brent launches (pm_kernel_stats).  brent: k_vdn_brent or k_vdn_brent_x of
+// T threads on the term list V.  (Templates over the kernel and its term list: C++ linkage inside this file's extern "C".)
+extern "C++" template <class K, class VA>
+static int launch_vdn_brent(pm_engine* E, const DevArgs& A, K brent, int max_grid, int T, size_t lds, const VA& V) {
+  const int grid = std::max(1, std::min(max_grid, A.n));
   if (int rc = mark(E, E->brent_events, true)) return rc;
-  hipLaunchKernelGGL(E->vdn_T == 64 ? k_vdn_brent<64> : k_vdn_brent<256>, dim3(grid), dim3(E->vdn_T), E->vdn_lds, E->stream, A, V);
+  hipLaunchKernelGGL(brent, dim3(grid), dim3(T), lds, E->stream, A, V);
   HIP_TRY(hipGetLastError());
   if (int rc = mark(E, E->brent_events, false)) return rc;
   hipLaunchKernelGGL(k_finalize_vdn, dim3((A.n + 255) / 256), dim3(256), 0, E->stream, A);
   HIP_TRY(hipGetLastError());
-  if (E->vw_fam_k > 0 || E->vw_car_k > 0) {   // the rows (DQ at or above the threshold), then their families and children
-    VdnWhoArgs W;
-    W.fam_k = E->vw_fam_k; W.car_k = E->vw_car_k; W.row_site = E->d_vw_row_site;
-    W.fam_top = E->d_vw_fam_top; W.fam_sum = E->d_vw_fam_sum; W.fam_all = E->d_vw_fam_all; W.fam_line = E->d_vw_fam_line;
-    W.pfam = E->d_vw_pfam; W.car_top = E->d_vw_car_top; W.car_all = E->d_vw_car_all; W.car_line = E->d_vw_car_line;
-    W.kids = E->d_vw_kids; W.n_nuc = E->vw_n_nuc; W.n_es = E->vw_n_es; W.is_kid = E->d_vw_is_kid; W.jbuf = E->d_vw_jbuf;
-    hipLaunchKernelGGL(k_vdn_rows, dim3(1), dim3(1024), 0, E->stream, A, E->d_vw_row_site);
-    HIP_TRY(hipGetLastError());
-    // (blocks beyond the row count leave at once; the peel workspace is k_vdn_brent's, sized for vdn_grid >= vw_grid blocks)
-    const int wgrid = std::max(1, std::min(E->vw_grid, A.n));
-    hipLaunchKernelGGL(E->vdn_T == 64 ? k_vdn_who<64> : k_vdn_who<256>, dim3(wgrid), dim3(E->vdn_T), 0, E->stream, A, V, W);
-    HIP_TRY(hipGetLastError());
-  }
   return PM_OK;
+}
+
+// pm_engine_set_vcf_denovo_detail's buffers and the autosomal children (chrX: launch_vcf_denovo_x puts its own in)
+static VdnWhoArgs vdn_who_args(const pm_engine* E) {
+  VdnWhoArgs W;
+  W.fam_k = E->vw_fam_k; W.car_k = E->vw_car_k; W.row_site = E->d_vw_row_site;
+  W.fam_top = E->d_vw_fam_top; W.fam_sum = E->d_vw_fam_sum; W.fam_all = E->d_vw_fam_all; W.fam_line = E->d_vw_fam_line;
+  W.pfam = E->d_vw_pfam; W.car_top = E->d_vw_car_top; W.car_all = E->d_vw_car_all; W.car_line = E->d_vw_car_line;
+  W.kids = E->d_vw_kids; W.n_nuc = E->vw_n_nuc; W.n_es = E->vw_n_es; W.is_kid = E->d_vw_is_kid; W.jbuf = E->d_vw_jbuf;
+  return W;
+}
+
+// The rows (DQ at or above the threshold), then their families and children.  who: k_vdn_who or k_vdn_who_x of T threads;
+// blocks beyond the row count leave at once.
+extern "C++" template <class K, class VA>
+static int launch_vdn_who(pm_engine* E, const DevArgs& A, K who, int max_grid, int T, const VA& V, const VdnWhoArgs& W) {
+  hipLaunchKernelGGL(k_vdn_rows, dim3(1), dim3(1024), 0, E->stream, A, E->d_vw_row_site);
+  HIP_TRY(hipGetLastError());
+  const int wgrid = std::max(1, std::min(max_grid, A.n));
+  hipLaunchKernelGGL(who, dim3(wgrid), dim3(T), 0, E->stream, A, V, W);
+  HIP_TRY(hipGetLastError());
+  return PM_OK;
+}
+
+// An autosomal section (pm_engine_set_vcf_denovo), and with pm_engine_set_vcf_denovo_detail on the rows and k_vdn_who.
+static int launch_vcf_denovo(pm_engine* E, const DevArgs& A) {
+  VdnArgs V;
+  V.terms = E->d_vdn_terms; V.n_terms = E->vdn_terms; V.n_peel = E->vdn_peel; V.n_nuc = E->vdn_nuc;
+  V.co_lds = E->vdn_lds > 0; V.co = E->d_vdn_co; V.ws = E->d_vdn_ws;
+  if (int rc = launch_vdn_brent(E, A, E->vdn_T == 64 ? k_vdn_brent<64> : k_vdn_brent<256>, E->vdn_grid, E->vdn_T, E->vdn_lds, V)) return rc;
+  if (E->vw_fam_k <= 0 && E->vw_car_k <= 0) return PM_OK;
+  // (the peel workspace is k_vdn_brent's, sized for vdn_grid >= vw_grid blocks)
+  return launch_vdn_who(E, A, E->vdn_T == 64 ? k_vdn_who<64> : k_vdn_who<256>, E->vw_grid, E->vdn_T, V, vdn_who_args(E));
 }
 
 // The same on a chrX section (pm_engine_set_vcf_denovo_chrx): k_vdn_brent_x on its own terms and workspace, then
@@ -1164,27 +1183,12 @@ static int launch_vcf_denovo_x(pm_engine* E, const DevArgs& A) {
   VdnXArgs V;
   V.terms = E->d_vdnx_terms; V.n_terms = E->vdnx_terms; V.n_peel = E->vdnx_peel; V.ws = E->d_vdnx_ws;
   for (int i = 0; i < 16; i++) V.a4[i] = E->A4_h[i];
-  const int grid = std::max(1, std::min(E->vdnx_grid, A.n));
-  if (int rc = mark(E, E->brent_events, true)) return rc;
-  hipLaunchKernelGGL(E->vdnx_T == 64 ? k_vdn_brent_x<64> : k_vdn_brent_x<256>, dim3(grid), dim3(E->vdnx_T), 0, E->stream, A, V);
-  HIP_TRY(hipGetLastError());
-  if (int rc = mark(E, E->brent_events, false)) return rc;
-  hipLaunchKernelGGL(k_finalize_vdn, dim3((A.n + 255) / 256), dim3(256), 0, E->stream, A);
-  HIP_TRY(hipGetLastError());
-  if (E->vwx_on) {
-    VdnWhoArgs W;
-    W.fam_k = E->vw_fam_k; W.car_k = E->vw_car_k; W.row_site = E->d_vw_row_site;
-    W.fam_top = E->d_vw_fam_top; W.fam_sum = E->d_vw_fam_sum; W.fam_all = E->d_vw_fam_all; W.fam_line = E->d_vw_fam_line;
-    W.pfam = E->d_vw_pfam; W.car_top = E->d_vw_car_top; W.car_all = E->d_vw_car_all; W.car_line = E->d_vw_car_line;
-    W.kids = E->d_vwx_kids; W.n_nuc = 0; W.n_es = E->vwx_n_kids; W.is_kid = E->d_vwx_is_kid; W.jbuf = E->d_vwx_jbuf;
-    hipLaunchKernelGGL(k_vdn_rows, dim3(1), dim3(1024), 0, E->stream, A, E->d_vw_row_site);
-    HIP_TRY(hipGetLastError());
-    // (vwx_grid <= vdnx_grid, the blocks of k_vdn_brent_x's workspace, and <= vw_grid, the blocks of the detail's lines)
-    const int wgrid = std::max(1, std::min(E->vwx_grid, A.n));
-    hipLaunchKernelGGL(E->vdnx_T == 64 ? k_vdn_who_x<64> : k_vdn_who_x<256>, dim3(wgrid), dim3(E->vdnx_T), 0, E->stream, A, V, W);
-    HIP_TRY(hipGetLastError());
-  }
-  return PM_OK;
+  if (int rc = launch_vdn_brent(E, A, E->vdnx_T == 64 ? k_vdn_brent_x<64> : k_vdn_brent_x<256>, E->vdnx_grid, E->vdnx_T, 0, V)) return rc;
+  if (!E->vwx_on) return PM_OK;
+  VdnWhoArgs W = vdn_who_args(E);
+  W.kids = E->d_vwx_kids; W.n_nuc = 0; W.n_es = E->vwx_n_kids; W.is_kid = E->d_vwx_is_kid; W.jbuf = E->d_vwx_jbuf;
+  // (vwx_grid <= vdnx_grid, the blocks of k_vdn_brent_x's workspace, and <= vw_grid, the blocks of the detail's lines)
+  return launch_vdn_who(E, A, E->vdnx_T == 64 ? k_vdn_who_x<64> : k_vdn_who_x<256>, E->vwx_grid, E->vdnx_T, V, W);
 }
 
 // The posterior plane of a vcf_mode batch's rows (vcf_post_dev.h): one more pass behind the standard posterior stage, with
@@ -1599,6 +1603,30 @@ int pm_engine_set_vcf_denovo_chrx(pm_engine* E, int32_t on) {
   return PM_OK;
 }
 
+// The children {family, member} of every family with offspring: every person with both parents in the family; is_kid[p]
+// = 1 for the persons listed.  nuc_first: the nuclear families take the closed form, so their children come first (the
+// count is returned), then the peeled families'; else one list in family order.
+static int vdn_list_children(const pm_engine* E, bool nuc_first, std::vector<int2>& kids, std::vector<int8_t>& is_kid) {
+  std::vector<int2> kids_es;
+  kids.clear();
+  is_kid.assign((size_t)E->n_person, 0);
+  for (int f = 0; f < E->n_fam; f++) {
+    const int kind = E->fam_kind_h[f], p0 = E->fam_start_h[f], n = E->fam_start_h[f + 1] - p0;
+    if (kind == PM_FAM_FOUNDERS) continue;
+    const bool closed = nuc_first && kind == PM_FAM_NUCLEAR;
+    for (int j = 0; j < n; j++) {
+      const int fa = E->fa_h[p0 + j], mo = E->mo_h[p0 + j];
+      if (fa < 0 || mo < 0 || fa >= n || mo >= n || fa == mo) continue;
+      if (closed && (j < 2 || fa > 1 || mo > 1)) continue;   // (a nuclear family is father, mother, kids)
+      (closed ? kids : kids_es).push_back(make_int2(f, j));
+      is_kid[p0 + j] = 1;
+    }
+  }
+  const int n_closed = (int)kids.size();
+  kids.insert(kids.end(), kids_es.begin(), kids_es.end());
+  return n_closed;
+}
+
 int pm_engine_set_vcf_denovo_detail(pm_engine* E, int32_t fam_k, int32_t car_k, int32_t want_all) {
   if (!E) { pm_set_last_error("pm_engine_set_vcf_denovo_detail: invalid arguments"); return PM_EINVAL; }
   if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_denovo_detail: the engine was created without vcf_mode"); return PM_EINVAL; }
@@ -1624,26 +1652,13 @@ int pm_engine_set_vcf_denovo_detail(pm_engine* E, int32_t fam_k, int32_t car_k, 
   vwx_free(E);   // (it writes into the buffers rebuilt here)
   vw_free(E);
   if (fam_k == 0 && car_k == 0) return PM_OK;
-  // the children: every person with both parents in the family, of the closed-form nuclear families (k_vdn_brent's
-  // routing: n_fam > 1), then of the peeled ones
-  std::vector<int2> kids, kids_es;
-  std::vector<int8_t> is_kid(np, 0);
+  // the children of the closed-form nuclear families (k_vdn_brent's routing: n_fam > 1), then of the peeled ones
+  std::vector<int2> kids;
+  std::vector<int8_t> is_kid;
+  const int n_nuc = vdn_list_children(E, E->n_fam > 1, kids, is_kid), n_es = (int)kids.size() - n_nuc;
   std::vector<int> pfam(np, 0);
-  for (int f = 0; f < E->n_fam; f++) {
-    const int kind = E->fam_kind_h[f], p0 = E->fam_start_h[f], n = E->fam_start_h[f + 1] - p0;
-    for (int j = 0; j < n; j++) pfam[p0 + j] = f;
-    if (kind == PM_FAM_FOUNDERS) continue;
-    const bool closed = kind == PM_FAM_NUCLEAR && E->n_fam > 1;
-    for (int j = 0; j < n; j++) {
-      const int fa = E->fa_h[p0 + j], mo = E->mo_h[p0 + j];
-      if (fa < 0 || mo < 0 || fa >= n || mo >= n || fa == mo) continue;
-      if (closed && (j < 2 || fa > 1 || mo > 1)) continue;   // (a nuclear family is father, mother, kids)
-      (closed ? kids : kids_es).push_back(make_int2(f, j));
-      is_kid[p0 + j] = 1;
-    }
-  }
-  const int n_nuc = (int)kids.size(), n_es = (int)kids_es.size();
-  kids.insert(kids.end(), kids_es.begin(), kids_es.end());
+  for (int f = 0; f < E->n_fam; f++)
+    for (int p = E->fam_start_h[f]; p < E->fam_start_h[f + 1]; p++) pfam[p] = f;
   // one block per row at a time, on k_vdn_brent's workspace (vdn_grid blocks); the peeled children's term buffer caps the
   // grid at 256 MiB
   int grid = E->vdn_grid;
@@ -1688,21 +1703,12 @@ int pm_engine_set_vcf_denovo_chrx_detail(pm_engine* E, int32_t on) {
   HIP_TRY(hipStreamSynchronize(E->stream));
   vwx_free(E);
   if (!on) return PM_OK;
-  // the children: every person with both parents in the family, of every family with offspring (all peeled on X:
-  // k_vdn_brent_x's routing, so the autosomal list's closed-form group does not apply)
+  // the children of every family with offspring (all peeled on X: k_vdn_brent_x's routing, so the autosomal list's
+  // closed-form group does not apply)
   const size_t np = (size_t)E->n_person;
   std::vector<int2> kids;
-  std::vector<int8_t> is_kid(np, 0);
-  for (int f = 0; f < E->n_fam; f++) {
-    const int p0 = E->fam_start_h[f], n = E->fam_start_h[f + 1] - p0;
-    if (E->fam_kind_h[f] == PM_FAM_FOUNDERS) continue;
-    for (int j = 0; j < n; j++) {
-      const int fa = E->fa_h[p0 + j], mo = E->mo_h[p0 + j];
-      if (fa < 0 || mo < 0 || fa >= n || mo >= n || fa == mo) continue;
-      kids.push_back(make_int2(f, j));
-      is_kid[p0 + j] = 1;
-    }
-  }
+  std::vector<int8_t> is_kid;
+  vdn_list_children(E, false, kids, is_kid);
   // one block per row at a time on k_vdn_brent_x's workspace (vdnx_grid blocks) and the detail's per-block lines (vw_grid
   // blocks); the children's term buffer caps the grid at 256 MiB
   int grid = std::min(E->vdnx_grid, E->vw_grid);

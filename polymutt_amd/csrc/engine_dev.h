@@ -3520,6 +3520,68 @@ __device__ __forceinline__ bool fam_lr_before(double la, int fa, double lb, int 
   return fa != INT_MAX && (fb == INT_MAX || la > lb || (la == lb && fa < fb));
 }
 
+// The fixed trees of the sums and rankings, for a block of T threads (T / 64 <= 4 waves): per-thread serial, xor
+// butterfly within a wave, the waves' partials from LDS (red / redf [2][4], the half par, flipped per use so that one
+// barrier per reduction is enough) in wave order.  Every thread of the block calls them.
+
+// the block's sum of part, written to *out by thread 0
+template <int T>
+__device__ __forceinline__ void block_sum_fixed(double part, double (*red)[4], int& par, double* out) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+  if ((threadIdx.x & 63) == 0) red[par][threadIdx.x >> 6] = part;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = red[par][0];
+#pragma unroll
+    for (int w = 1; w < T / 64; w++) s += red[par][w];
+    *out = s;
+  }
+  par ^= 1;
+}
+
+// the block's best (value, index) by fam_lr_before, in every thread
+template <int T>
+__device__ __forceinline__ void block_best(double& bl, int& bf, double (*red)[4], int (*redf)[4], int& par) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ol = __shfl_xor(bl, o, 64);
+    const int of = __shfl_xor(bf, o, 64);
+    if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
+  }
+  if ((threadIdx.x & 63) == 0) { red[par][threadIdx.x >> 6] = bl; redf[par][threadIdx.x >> 6] = bf; }
+  __syncthreads();
+  bl = red[par][0]; bf = redf[par][0];
+#pragma unroll
+  for (int w = 1; w < T / 64; w++)
+    if (fam_lr_before(red[par][w], redf[par][w], bl, bf)) { bl = red[par][w]; bf = redf[par][w]; }
+  par ^= 1;
+}
+
+// The top_k ranking of n candidates: round k takes the best entry that comes after round k - 1's in the order.
+// cand(q, d) gives candidate q's index (< 0: none) and sets its value d; thread 0 calls emit(k, value, index) with
+// index INT_MAX where the round found nothing.
+template <int T, class Cand, class Emit>
+__device__ __forceinline__ void block_top_k(int top_k, int n, double (*red)[4], int (*redf)[4], int& par, Cand cand, Emit emit) {
+  double prev_v = 0.0;
+  int prev_i = -1;
+  for (int k = 0; k < top_k; k++) {
+    double bl = 0.0;
+    int bf = INT_MAX;
+    for (int q = threadIdx.x; q < n; q += blockDim.x) {   // (= T, read at run time: with the constant k_fam_dnlr<true> spills 8 bytes more)
+      double d;
+      const int i = cand(q, d);
+      if (i < 0) continue;
+      const bool after = k == 0 ? d == d : (d < prev_v || (d == prev_v && i > prev_i));
+      if (after && fam_lr_before(d, i, bl, bf)) { bl = d; bf = i; }
+    }
+    block_best<T>(bl, bf, red, redf, par);
+    if (threadIdx.x == 0) emit(k, bl, bf);
+    if (bf == INT_MAX) { prev_v = -INFINITY; prev_i = INT_MAX; }   // exhausted: every later round is empty too
+    else { prev_v = bl; prev_i = bf; }
+  }
+}
+
 template <bool ES>
 __global__ void __launch_bounds__(256) k_fam_dnlr(DevArgs A, FamLrArgs F) {
   __shared__ double s_lk[256];
@@ -3530,7 +3592,6 @@ __global__ void __launch_bounds__(256) k_fam_dnlr(DevArgs A, FamLrArgs F) {
   for (int i = threadIdx.x; i < 100; i += blockDim.x) s_M[i] = A.M[i];
   __syncthreads();
   const int rows = A.counts[3], np = A.n_person, nf = A.n_fam;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const size_t ws_stride = (size_t)gridDim.x * blockDim.x;
   double* wsl = ES ? A.ws + (size_t)blockIdx.x * blockDim.x + threadIdx.x : nullptr;
   (void)wsl; (void)ws_stride;
@@ -3614,46 +3675,14 @@ __global__ void __launch_bounds__(256) k_fam_dnlr(DevArgs A, FamLrArgs F) {
       line[f] = D;
       part += D;
     }
-    // the row's sum
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-    if (lane == 0) s_red[par][wv] = part;
-    __syncthreads();
-    if (threadIdx.x == 0) F.sum[row] = ((s_red[par][0] + s_red[par][1]) + s_red[par][2]) + s_red[par][3];
-    par ^= 1;
-    // the ranking: round k takes the best entry that comes after round k - 1's in the order
-    double prev_lr = 0.0;
-    int prev_f = -1;
-    for (int k = 0; k < F.top_k; k++) {
-      double bl = 0.0;
-      int bf = INT_MAX;
-      for (int fi = threadIdx.x; fi < nf; fi += blockDim.x) {
-        const int f = A.fam_perm[fi];
-        const double d = line[f];   // (written by this thread above)
-        const bool after = k == 0 ? d == d : (d < prev_lr || (d == prev_lr && f > prev_f));
-        if (after && fam_lr_before(d, f, bl, bf)) { bl = d; bf = f; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double ol = __shfl_xor(bl, o, 64);
-        const int of = __shfl_xor(bf, o, 64);
-        if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
-      }
-      if (lane == 0) { s_red[par][wv] = bl; s_redf[par][wv] = bf; }
-      __syncthreads();
-      bl = s_red[par][0]; bf = s_redf[par][0];
-#pragma unroll
-      for (int w = 1; w < 4; w++)
-        if (fam_lr_before(s_red[par][w], s_redf[par][w], bl, bf)) { bl = s_red[par][w]; bf = s_redf[par][w]; }
-      par ^= 1;
-      if (threadIdx.x == 0) {
+    block_sum_fixed<256>(part, s_red, par, F.sum + row);   // the row's sum
+    block_top_k<256>(F.top_k, nf, s_red, s_redf, par,
+      [&](int fi, double& d) { const int f = A.fam_perm[fi]; d = line[f]; return f; },   // (written by this thread above)
+      [&](int k, double lr, int f) {
         pm_fam_lr o;
-        o.fam = bf == INT_MAX ? -1 : bf; o.pad = 0; o.lr = bf == INT_MAX ? 0.0 : bl;
+        o.fam = f == INT_MAX ? -1 : f; o.pad = 0; o.lr = f == INT_MAX ? 0.0 : lr;
         F.top[(size_t)row * F.top_k + k] = o;
-      }
-      if (bf == INT_MAX) { prev_lr = -INFINITY; prev_f = INT_MAX; }   // exhausted: every later round is empty too
-      else { prev_lr = bl; prev_f = bf; }
-    }
+      });
   }
 }
 
@@ -3712,7 +3741,6 @@ __global__ void __launch_bounds__(256) k_person_dn(DevArgs A, PersonDnArgs P) {
   for (int i = threadIdx.x; i < 100; i += blockDim.x) s_M[i] = A.M[i];
   __syncthreads();
   const int rows = A.counts[3], np = A.n_person, nk = P.n_nuc + P.n_es;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const size_t ws_stride = (size_t)gridDim.x * blockDim.x;
   double* wsl = ES ? A.ws + (size_t)blockIdx.x * blockDim.x + threadIdx.x : nullptr;
   double* jb = ES ? P.jbuf + (size_t)blockIdx.x * P.n_es * 111 : nullptr;
@@ -3870,40 +3898,14 @@ __global__ void __launch_bounds__(256) k_person_dn(DevArgs A, PersonDnArgs P) {
       }
     }
     __syncthreads();   // the row's entries are visible to the block: the ranking reads what other threads wrote
-    double prev_pp = 0.0;
-    int prev_p = -1;
-    for (int k = 0; k < P.top_k; k++) {   // round k takes the best entry that comes after round k - 1's in the order
-      double bl = 0.0;
-      int bf = INT_MAX;
-      for (int i = threadIdx.x; i < nk; i += blockDim.x) {
-        const int2 kd = P.kids[i];
-        const int p = A.fam_start[kd.x] + kd.y;
-        const double d = line[p].pp;
-        const bool after = k == 0 ? d == d : (d < prev_pp || (d == prev_pp && p > prev_p));
-        if (after && fam_lr_before(d, p, bl, bf)) { bl = d; bf = p; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double ol = __shfl_xor(bl, o, 64);
-        const int of = __shfl_xor(bf, o, 64);
-        if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
-      }
-      if (lane == 0) { s_red[par][wv] = bl; s_redf[par][wv] = bf; }
-      __syncthreads();
-      bl = s_red[par][0]; bf = s_redf[par][0];
-#pragma unroll
-      for (int w = 1; w < 4; w++)
-        if (fam_lr_before(s_red[par][w], s_redf[par][w], bl, bf)) { bl = s_red[par][w]; bf = s_redf[par][w]; }
-      par ^= 1;
-      if (threadIdx.x == 0) {
+    block_top_k<256>(P.top_k, nk, s_red, s_redf, par,
+      [&](int i, double& d) { const int2 kd = P.kids[i]; const int p = A.fam_start[kd.x] + kd.y; d = line[p].pp; return p; },
+      [&](int k, double, int p) {
         pm_person_dn o;
         o.person = -1; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
-        if (bf != INT_MAX) o = line[bf];
+        if (p != INT_MAX) o = line[p];
         P.top[(size_t)row * P.top_k + k] = o;
-      }
-      if (bf == INT_MAX) { prev_pp = -INFINITY; prev_p = INT_MAX; }   // exhausted: every later round is empty too
-      else { prev_pp = bl; prev_p = bf; }
-    }
+      });
     __syncthreads();   // (the next row rewrites the block's line and jbuf)
   }
 }

@@ -17,6 +17,15 @@
 // One block per item; the block's threads take the terms (a peeled family, a nuclear family or a founder person each)
 // round robin, the per-thread products are combined by vdn_logprod (fixed order, one log10 per evaluation), and the
 // item runs OptimizeFrequency + Brent through brent_core.h's state machine like every other item.
+//
+// The autosomal and the chrX kernels (k_vdn_brent / k_vdn_brent_x, and k_vdn_who / k_vdn_who_x for the families and
+// children behind each DQ) differ in their term lists and argument structs and stay apart; what they compute alike is
+// written once, with the chrX model behind a template parameter X: the peel (d_es_lk3_vdn), lkSinglePerson
+// (vdn_person_lk) and a founders-only family's product of it (vdn_founders_lk), the per-site tables of the two who
+// kernels (vdn_tables), stages B and C of their clamped peels (vdn_stage_b, vdn_stage_c) and their sums and rankings
+// (vdn_rank_fams, vdn_rank_kids, on engine_dev.h's block_sum_fixed and block_top_k).  The two Brent kernels keep their
+// own text of the table set-up, and k_vdn_brent of the nuclear closed form (vdn_nuc_lk holds the other): with either
+// behind a shared function the compiler schedules the Brent kernels differently, and they are the ones a run waits for.
 #pragma once
 
 enum VdnTerm { VT_PEEL = 0, VT_NUC = 1, VT_PERSON = 2 };
@@ -29,13 +38,17 @@ struct VdnArgs {
   double* ws;         // peel workspace [grid][ws_per_lane][T], lane-interleaved like DevArgs::ws
 };
 
-// d_es_lk<3> on an autosome with the transmission tables passed in (LDS): tdn where the de novo model mutates, tba elsewhere
+__device__ __forceinline__ int vdn_pick3(const int* g, int s) { return s == 0 ? g[0] : s == 1 ? g[1] : g[2]; }
+
+// d_es_lk<3> with the transmission tables passed in (LDS): tdn where the de novo model mutates, tpl (plain) elsewhere.
+// X: the chrX model -- a male founder takes the prior (f, 0, 1 - f) and the tables are picked by the sex of the step's
+// child, t[0] to a daughter (or a child of unknown sex), t[27] to a son; without X one autosomal table each.
 // CL: three more persons c0, c1, c2 (family-local indices) are clamped to the state sets m0, m1, m2 (bit s = state s of
-// (g11, g12, g22) allowed), where the initial partials are filled, as d_es_lk<10, true> does (k_vdn_who); without CL
-// nothing is added.
-template <bool CL = false>
+// (g11, g12, g22) allowed), where the initial partials are filled, as d_es_lk<10, true> does (k_vdn_who, k_vdn_who_x);
+// without CL nothing is added.
+template <bool CL = false, bool X = false>
 __device__ __forceinline__ double d_es_lk3_vdn(const DevArgs& A, int f, const uint8_t* pl, const double* lk, const int* gidx, double freq,
-                                               const double* tdn, const double* tba, double* ws, size_t st, int c0 = -1, int m0 = 0,
+                                               const double* tdn, const double* tpl, double* ws, size_t st, int c0 = -1, int m0 = 0,
                                                int c1 = -1, int m1 = 0, int c2 = -1, int m2 = 0) {
   const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0, nf = A.fam_founders[f];
 #define PP(i, j) ws[((size_t)(i) * 3 + (j)) * st]
@@ -45,7 +58,10 @@ __device__ __forceinline__ double d_es_lk3_vdn(const DevArgs& A, int f, const ui
     const bool fo = A.is_founder[p0 + i] != 0;
     const uint8_t* R = pl + p0 + i;   // plane g at R[g * n_person]
     double pr[3] = {0.0, 0.0, 0.0};
-    if (i < nf) { pr[0] = freq * freq; pr[1] = 2 * freq * (1 - freq); pr[2] = (1 - freq) * (1 - freq); }
+    if (i < nf) {
+      pr[0] = freq * freq; pr[1] = 2 * freq * (1 - freq); pr[2] = (1 - freq) * (1 - freq);
+      if (X && A.sex[p0 + i] == MALE) { pr[0] = freq; pr[1] = 0; pr[2] = 1 - freq; }
+    }
 #pragma unroll
     for (int j = 0; j < 3; j++) {
       double pen = lk[R[gidx[j] * np]];
@@ -59,9 +75,10 @@ __device__ __forceinline__ double d_es_lk3_vdn(const DevArgs& A, int f, const ui
     const int2 S = A.steps[s];
     const int type = S.x & 255, from0 = (S.x >> 8) & 255, from1 = (S.x >> 16) & 255, to0 = (S.x >> 24) & 255;
     const int slot = (S.y >> 8) & 255, create = (S.y >> 16) & 1, fa2mo = (S.y >> 17) & 1;
-    if (type == 1) {   // offspring -> parents: transmission_denovo
+    if (type == 1) {   // offspring -> parents: transmission_denovo (X: of the child's sex)
       if (create)
         for (int x = 0; x < 9; x++) MPP(slot, x / 3, x % 3) = 1.0;
+      const double* tt = tdn + (X && A.sex[p0 + from0] == MALE ? 27 : 0);
       double pk[3];
 #pragma unroll
       for (int k = 0; k < 3; k++) pk[k] = PP(from0, k);
@@ -69,7 +86,7 @@ __device__ __forceinline__ double d_es_lk3_vdn(const DevArgs& A, int f, const ui
         for (int j = 0; j < 3; j++) {
           double sum = 0;
 #pragma unroll
-          for (int k = 0; k < 3; k++) sum += tdn[(i * 3 + j) * 3 + k] * pk[k];
+          for (int k = 0; k < 3; k++) sum += tt[(i * 3 + j) * 3 + k] * pk[k];
           MPP(slot, i, j) *= sum;
         }
     } else if (type == 2) {   // spouse -> spouse
@@ -84,7 +101,7 @@ __device__ __forceinline__ double d_es_lk3_vdn(const DevArgs& A, int f, const ui
         PP(to0, i) *= sum;
       }
     } else {   // parents -> only offspring: transmission_denovo without a marriage partial, plain transmission with one
-      const double* tt = slot == 255 ? tdn : tba;
+      const double* tt = (slot == 255 ? tdn : tpl) + (X && A.sex[p0 + to0] == MALE ? 27 : 0);
       double pf[3], pm[3], sum[3];
 #pragma unroll
       for (int k = 0; k < 3; k++) { pf[k] = PP(from0, k); pm[k] = PP(from1, k); sum[k] = 0.0; }
@@ -128,6 +145,37 @@ __device__ __forceinline__ double vdn_logprod(double m, int e, double* red, int*
   }
   if (e >= -1 && e <= 1) return log10(ldexp(m, e));
   return log10_mant_u(m, e);
+}
+
+// The per-site tables of a record with the alleles (a1, a2): m3 = M3, on X h3 = H3 (the haploid mutation matrix: the
+// 2 x 2 block of the allele mutation matrix a4 on states 0 and 2, row and column 1 zero), and tdn = the plain table(s)
+// tpl followed by them -- [0..26] T M3 (on X: to a daughter), on X [27..53] to a son, followed by H3.  Every thread of
+// the block calls it (k_vdn_who, k_vdn_who_x); the tables are written when it returns.
+template <bool X>
+__device__ __forceinline__ void vdn_tables(const int* gidx, int a1, int a2, const double* M, const double* a4, const double* tpl,
+                                           double* m3, double* h3, double* tdn) {
+  __syncthreads();   // (the previous row no longer reads the tables, the lines or jbuf; tpl is written)
+  if (threadIdx.x < 9) {
+    const int x = threadIdx.x / 3, y = threadIdx.x % 3;
+    m3[threadIdx.x] = M[vdn_pick3(gidx, x) * 10 + vdn_pick3(gidx, y)];
+    if (X) h3[threadIdx.x] = (x == 1 || y == 1) ? 0.0 : a4[(((x ? a2 : a1) - 1) & 3) * 4 + (((y ? a2 : a1) - 1) & 3)];   // (bases are 1..4)
+  }
+  __syncthreads();
+  if (threadIdx.x < (X ? 54 : 27)) {
+    const int ij = (X ? threadIdx.x % 27 : threadIdx.x) / 3, k = threadIdx.x % 3;
+    const double* tp = tpl + (!X || threadIdx.x < 27 ? 0 : 27);
+    const double* mm = !X || threadIdx.x < 27 ? m3 : h3;
+    double s = 0.0;
+    for (int m = 0; m < 3; m++) s += tp[ij * 3 + m] * mm[m * 3 + k];
+    tdn[threadIdx.x] = s;
+  }
+  __syncthreads();
+}
+
+// lkSinglePerson at the frequency x (g = 1 - x) of a person with the likelihoods (l11, l12, l22): a male on X is hemizygous
+template <bool X>
+__device__ __forceinline__ double vdn_person_lk(double l11, double l12, double l22, bool male, double x, double g) {
+  return X && male ? l11 * x + l22 * g : l11 * (x * x) + l12 * (2 * x * g) + l22 * (g * g);
 }
 
 // The de novo Brent item of every site of list 0 (the called sites of a vcf_mode batch): results to raw / minv / evals
@@ -272,96 +320,15 @@ __global__ void __launch_bounds__(256) k_finalize_vdn(DevArgs A) {
 // ------------------------------------------------------------------------------------------------
 // chrX (pm_engine_set_vcf_denovo_chrx): the sex-aware three-state model of include/polymutt_engine.h.  A male carries the
 // states 0 and 2 only (hemizygous a1, a2), so a son's transmission c_TBA[2] is followed by the haploid mutation matrix
-// H3 (the 2 x 2 block of the allele mutation matrix A4 on states 0 and 2, row and column 1 zero) and a daughter's
-// c_TBA[1] by M3; male founders take the prior (f, 0, 1 - f).  There is no closed form on X: every family with offspring
-// is peeled on every evaluation (vcf_mode's plan 1 routing), a founders-only family is the product of its persons.
-__device__ __forceinline__ int vdn_pick3(const int* g, int s);
+// H3 and a daughter's c_TBA[1] by M3 (vdn_tables<true>); male founders take the prior (f, 0, 1 - f).  There is no closed
+// form on X: every family with offspring is peeled on every evaluation (vcf_mode's plan 1 routing), a founders-only
+// family is the product of its persons.
 struct VdnXArgs {
   const int* terms;   // [n_terms] n_peel peeled families (every family with offspring), then the persons of founders-only families
   int n_terms, n_peel;
   double* ws;         // peel workspace [grid][ws_per_lane][T], lane-interleaved like DevArgs::ws
   double a4[16];      // the allele mutation matrix of denovo_mut_rate / denovo_tstv (the one M is built from)
 };
-
-// d_es_lk<3> on chrX with the transmission tables passed in (LDS), picked by the sex of the step's child: t[0] to a
-// daughter (or a child of unknown sex), t[27] to a son.  tdn where the de novo model mutates, tpl (plain) elsewhere.
-// CL: d_es_lk3_vdn<CL>'s clamps (k_vdn_who_x); without CL nothing is added.
-template <bool CL = false>
-__device__ __forceinline__ double d_es_lk3_vdn_x(const DevArgs& A, int f, const uint8_t* pl, const double* lk, const int* gidx, double freq,
-                                                 const double* tdn, const double* tpl, double* ws, size_t st, int c0 = -1, int m0 = 0,
-                                                 int c1 = -1, int m1 = 0, int c2 = -1, int m2 = 0) {
-  const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0, nf = A.fam_founders[f];
-#define PP(i, j) ws[((size_t)(i) * 3 + (j)) * st]
-#define MPP(sl, x, y) ws[((size_t)n * 3 + (size_t)(sl) * 9 + (x) * 3 + (y)) * st]
-  const size_t np = (size_t)A.n_person;
-  for (int i = 0; i < n; i++) {
-    const bool fo = A.is_founder[p0 + i] != 0;
-    const uint8_t* R = pl + p0 + i;   // plane g at R[g * n_person]
-    double pr[3] = {0.0, 0.0, 0.0};
-    if (i < nf) {
-      pr[0] = freq * freq; pr[1] = 2 * freq * (1 - freq); pr[2] = (1 - freq) * (1 - freq);
-      if (A.sex[p0 + i] == MALE) { pr[0] = freq; pr[1] = 0; pr[2] = 1 - freq; }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      double pen = lk[R[gidx[j] * np]];
-      if (CL)
-        if ((i == c0 && !((m0 >> j) & 1)) || (i == c1 && !((m1 >> j) & 1)) || (i == c2 && !((m2 >> j) & 1))) pen = 0.0;
-      PP(i, j) = fo ? pr[j] * pen : pen;
-    }
-  }
-  const int s0 = A.peel_start[f], s1 = A.peel_start[f + 1];
-  for (int s = s0; s < s1; s++) {
-    const int2 S = A.steps[s];
-    const int type = S.x & 255, from0 = (S.x >> 8) & 255, from1 = (S.x >> 16) & 255, to0 = (S.x >> 24) & 255;
-    const int slot = (S.y >> 8) & 255, create = (S.y >> 16) & 1, fa2mo = (S.y >> 17) & 1;
-    if (type == 1) {   // offspring -> parents: transmission_denovo of the child's sex
-      if (create)
-        for (int x = 0; x < 9; x++) MPP(slot, x / 3, x % 3) = 1.0;
-      const double* tt = tdn + (A.sex[p0 + from0] == MALE ? 27 : 0);
-      double pk[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) pk[k] = PP(from0, k);
-      for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-          double sum = 0;
-#pragma unroll
-          for (int k = 0; k < 3; k++) sum += tt[(i * 3 + j) * 3 + k] * pk[k];
-          MPP(slot, i, j) *= sum;
-        }
-    } else if (type == 2) {   // spouse -> spouse
-      double ps[3];
-#pragma unroll
-      for (int j = 0; j < 3; j++) ps[j] = PP(from0, j);
-      for (int i = 0; i < 3; i++) {
-        double sum = 0.0;
-        if (slot == 255) for (int j = 0; j < 3; j++) sum += ps[j];
-        else if (fa2mo) for (int j = 0; j < 3; j++) sum += ps[j] * MPP(slot, j, i);
-        else for (int j = 0; j < 3; j++) sum += ps[j] * MPP(slot, i, j);
-        PP(to0, i) *= sum;
-      }
-    } else {   // parents -> only offspring: transmission_denovo without a marriage partial, plain transmission with one
-      const double* tt = (slot == 255 ? tdn : tpl) + (A.sex[p0 + to0] == MALE ? 27 : 0);
-      double pf[3], pm[3], sum[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) { pf[k] = PP(from0, k); pm[k] = PP(from1, k); sum[k] = 0.0; }
-      for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-          const double w = (slot == 255) ? pf[i] * pm[j] : pf[i] * MPP(slot, i, j) * pm[j];
-#pragma unroll
-          for (int k = 0; k < 3; k++) sum[k] += w * tt[(i * 3 + j) * 3 + k];
-        }
-#pragma unroll
-      for (int k = 0; k < 3; k++) PP(to0, k) *= sum[k];
-    }
-  }
-  const int fin = (A.steps[s1 - 1].x >> 24) & 255;
-  double L = 0.0;
-  for (int i = 0; i < 3; i++) L += PP(fin, i);
-  return L;
-#undef PP
-#undef MPP
-}
 
 // The chrX de novo Brent item of every site of list 0: k_vdn_brent's outputs (raw / minv / evals slot 2, D to raw slot 3,
 // a stuck Brent to counts[5] / counts[6]) for k_finalize_vdn.  One block per item, the terms round robin over its threads.
@@ -417,15 +384,15 @@ __global__ void __launch_bounds__(T) k_vdn_brent_x(DevArgs A, VdnXArgs V) {
         int e = 0;
         for (int q = threadIdx.x; q < V.n_peel; q += T) {
           int e1, e2;
-          const double mv = frexp(d_es_lk3_vdn_x(A, V.terms[q], pl, s_lk, gidx, x, tt, s_tpl, ws, T), &e1);
+          const double mv = frexp(d_es_lk3_vdn<false, true>(A, V.terms[q], pl, s_lk, gidx, x, tt, s_tpl, ws, T), &e1);
           m = frexp(m * mv, &e2);
           e += e1 + e2;
         }
-        for (int q = V.n_peel + threadIdx.x; q < V.n_terms; q += T) {   // lkSinglePerson: a male is hemizygous
+        for (int q = V.n_peel + threadIdx.x; q < V.n_terms; q += T) {
           const int p = V.terms[q];
           const uint8_t* P = pl + p;
           const double l11 = s_lk[P[gidx[0] * np]], l12 = s_lk[P[gidx[1] * np]], l22 = s_lk[P[gidx[2] * np]];
-          const double v = A.sex[p] == MALE ? l11 * x + l22 * g : l11 * (x * x) + l12 * (2 * x * g) + l22 * (g * g);
+          const double v = vdn_person_lk<true>(l11, l12, l22, A.sex[p] == MALE, x, g);
           int e1, e2;
           const double mv = frexp(v, &e1);
           m = frexp(m * mv, &e2);
@@ -449,8 +416,9 @@ __global__ void __launch_bounds__(T) k_vdn_brent_x(DevArgs A, VdnXArgs V) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// The families and the children behind each DQ (pm_engine_set_vcf_denovo_detail).  A row is a called site with
-// evals[2] > 0 (the de novo item ran) and denovo_lr >= pm_params.denovo_min_llr; rows are numbered in site order.
+// The families and the children behind each DQ (pm_engine_set_vcf_denovo_detail, and on chrX
+// pm_engine_set_vcf_denovo_chrx_detail).  A row is a called site with evals[2] > 0 (the de novo item ran) and
+// denovo_lr >= pm_params.denovo_min_llr; rows are numbered in site order.
 struct VdnWhoArgs {
   int fam_k, car_k;         // 0 (that half is off) or 1..8
   int* row_site;            // [max_batch] row -> site (k_vdn_rows; the row count goes to counts[10])
@@ -463,7 +431,7 @@ struct VdnWhoArgs {
   pm_person_dn* car_all;    // [rows][n_person], or null
   pm_person_dn* car_line;   // [gridDim.x][n_person] when car_all is null
   const int2* kids;         // the non-founders {family, member}: n_nuc of closed-form nuclear families, then n_es of peeled ones
-  int n_nuc, n_es;
+  int n_nuc, n_es;          // (chrX: n_nuc = 0, every child is peeled)
   const int8_t* is_kid;     // [n_person] 1 = listed in kids
   double* jbuf;             // [gridDim.x][n_es * 13] clamped-peel values: 9 pairs, 3 single states, L_f
 };
@@ -520,16 +488,134 @@ __device__ __forceinline__ double vdn_nuc_lk(const uint8_t* P, size_t np, int n,
   return v;
 }
 
-// the family of term q of the VdnArgs list, -1 for a founder person that is not its family's first (that person's term
-// carries the whole founders-only family, summed in person order)
-__device__ __forceinline__ int vdn_term_fam(const DevArgs& A, const VdnArgs& V, const VdnWhoArgs& W, int q) {
-  const int x = V.terms[q];
-  if (q < V.n_peel + V.n_nuc) return x;
+// the family of term q of a list whose first n_fam_terms terms are families and whose others are founder persons, -1 for
+// a founder person that is not its family's first (that person's term carries the whole founders-only family)
+__device__ __forceinline__ int vdn_term_fam(const DevArgs& A, const int* terms, int n_fam_terms, const VdnWhoArgs& W, int q) {
+  const int x = terms[q];
+  if (q < n_fam_terms) return x;
   const int f = W.pfam[x];
   return x == A.fam_start[f] ? f : -1;
 }
 
-__device__ __forceinline__ int vdn_pick3(const int* g, int s) { return s == 0 ? g[0] : s == 1 ? g[1] : g[2]; }
+// A founders-only family at the frequencies xN and xD: the product of lkSinglePerson in person order, the same form in
+// both models, as normalised (mantissa, exponent) pairs
+template <bool X>
+__device__ __forceinline__ void vdn_founders_lk(const DevArgs& A, int f, const uint8_t* pl, const double* lk, const int* gidx, double xN,
+                                                double xD, double& mN, int& eN, double& mD, int& eD) {
+  const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0;
+  const size_t np = (size_t)A.n_person;
+  mN = 1.0; mD = 1.0; eN = 0; eD = 0;
+  const double gN = 1 - xN, gD = 1 - xD;
+  for (int j = 0; j < n; j++) {
+    const uint8_t* P = pl + p0 + j;
+    const double l11 = lk[P[gidx[0] * np]], l12 = lk[P[gidx[1] * np]], l22 = lk[P[gidx[2] * np]];
+    const bool male = X && A.sex[p0 + j] == MALE;
+    int e1;
+    mN = frexp(mN * vdn_person_lk<X>(l11, l12, l22, male, xN, gN), &e1);
+    eN += e1;
+    mD = frexp(mD * vdn_person_lk<X>(l11, l12, l22, male, xD, gD), &e1);
+    eD += e1;
+  }
+}
+
+// NonMendX(a, b, sex): the states a child of that sex can carry (a son 0 and 2, anyone else all three) that the plain
+// transmission from parents in states (a, b) gives probability 0, as a 3-bit mask.  tpl: [0..26] to a daughter, [27..53]
+// to a son.  Empty for a son of a heterozygous mother.
+__device__ __forceinline__ int vdnx_nonmend(const double* tpl, int k, bool male) {
+  const double* t = tpl + (male ? 27 : 0) + k * 3;
+  int m = 0;
+#pragma unroll
+  for (int s = 0; s < 3; s++)
+    if (!(male && s == 1) && t[s] == 0.0) m |= 1 << s;
+  return m;
+}
+
+// The rest of a row's family half, behind the loop that wrote the terms' D_f to line and summed them to part: the row's
+// sum and the top fam_k families.  term_fam(q): vdn_term_fam of the kernel's list.
+template <int T, class TermFam>
+__device__ __forceinline__ void vdn_rank_fams(const VdnWhoArgs& W, int row, const double* line, double part, int n_terms,
+                                              double (*red)[4], int (*redf)[4], int& par, TermFam term_fam) {
+  block_sum_fixed<T>(part, red, par, W.fam_sum + row);
+  block_top_k<T>(W.fam_k, n_terms, red, redf, par,
+    [&](int q, double& d) { const int f = term_fam(q); if (f >= 0) d = line[f]; return f; },   // (written by this thread above)
+    [&](int k, double lr, int f) {
+      pm_fam_lr o;
+      o.fam = f == INT_MAX ? -1 : f; o.pad = 0; o.lr = f == INT_MAX ? 0.0 : lr;
+      W.fam_top[(size_t)row * W.fam_k + k] = o;
+    });
+}
+
+// founders (and anyone without both parents) have no value in a row's line of children
+template <int T>
+__device__ __forceinline__ void vdn_clear_nonkids(const VdnWhoArgs& W, pm_person_dn* line, int np) {
+  for (int p = threadIdx.x; p < np; p += T)
+    if (!W.is_kid[p]) {
+      pm_person_dn o;
+      o.person = p; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
+      line[p] = o;
+    }
+}
+
+// Stage B of the clamped peels of the n_es children kids[] (jb: the block's jbuf, [n_es * 9] stage A's pair terms J, then
+// [n_es * 4] this stage's): per child the unclamped L_f, and the best pair's peels with the child clamped to each single
+// state of the pair's non-Mendelian set (-1 for the others).  X: the chrX peel and NonMendX of the child's sex.
+template <int T, bool X>
+__device__ __forceinline__ void vdn_stage_b(const DevArgs& A, const int2* kids, int n_es, const uint8_t* pl, const double* lk, const int* gidx,
+                                            double xN, const double* tdn, const double* tpl, double* ws, double* jb) {
+  double* jb2 = jb + (size_t)n_es * 9;
+  for (int it = threadIdx.x; it < n_es * 4; it += T) {
+    const int ci = it / 4, slot = it % 4;
+    const int2 kd = kids[ci];
+    const int p0 = A.fam_start[kd.x], jc = kd.y, fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
+    double v = -1.0;
+    if (slot == 3) v = d_es_lk3_vdn<false, X>(A, kd.x, pl, lk, gidx, xN, tdn, tpl, ws, T);
+    else {
+      double bj = 0.0;
+      int bi = -1;
+      for (int q = 0; q < 9; q++) { const double J = jb[ci * 9 + q]; if (J > bj) { bj = J; bi = q; } }
+      if (bi >= 0 && (((X ? vdnx_nonmend(tpl, bi, A.sex[p0 + jc] == MALE) : 7 & ~d_mend3(bi)) >> slot) & 1))
+        v = d_es_lk3_vdn<true, X>(A, kd.x, pl, lk, gidx, xN, tdn, tpl, ws, T, fa, 1 << (bi / 3), mo, 1 << (bi % 3), jc, 1 << slot);
+    }
+    jb2[it] = v;
+  }
+}
+
+// Stage C: one thread per child sums the nine pair terms in (a, b) order and names the event
+template <int T>
+__device__ __forceinline__ void vdn_stage_c(const DevArgs& A, const int2* kids, int n_es, const int* gidx, const double* jb, pm_person_dn* line) {
+  const double* jb2 = jb + (size_t)n_es * 9;
+  for (int ci = threadIdx.x; ci < n_es; ci += T) {
+    const int2 kd = kids[ci];
+    const int p = A.fam_start[kd.x] + kd.y;
+    double num = 0.0, bj = 0.0;
+    int bi = -1;
+    for (int q = 0; q < 9; q++) { const double J = jb[ci * 9 + q]; num += J; if (J > bj) { bj = J; bi = q; } }
+    const double L = jb2[ci * 4 + 3];
+    double bv = 0.0;
+    int bs = -1;
+    for (int s = 0; s < 3; s++) { const double v = jb2[ci * 4 + s]; if (v > bv) { bv = v; bs = s; } }
+    pm_person_dn o;
+    o.person = p; o.pad = 0;
+    o.fa_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bi / 3)); o.mo_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bi % 3));
+    o.kid_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bs));
+    o.pp = L > 0.0 ? fmin(num / L, 1.0) : 0.0;   // (L_f and the terms come from separate peels: rounding may pass 1)
+    line[p] = o;
+  }
+}
+
+// the top car_k of a row's children by pp (line: every child's entry, visible to the block)
+template <int T>
+__device__ __forceinline__ void vdn_rank_kids(const DevArgs& A, const VdnWhoArgs& W, int row, const pm_person_dn* line, double (*red)[4],
+                                              int (*redf)[4], int& par) {
+  block_top_k<T>(W.car_k, W.n_nuc + W.n_es, red, redf, par,
+    [&](int i, double& d) { const int2 kd = W.kids[i]; const int p = A.fam_start[kd.x] + kd.y; d = line[p].pp; return p; },
+    [&](int k, double, int p) {
+      pm_person_dn o;
+      o.person = -1; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
+      if (p != INT_MAX) o = line[p];
+      W.car_top[(size_t)row * W.car_k + k] = o;
+    });
+}
 
 // k_vdn_who: per row, in the three states of the record's (ref, alt) and the model of k_vdn_brent,
 //   D_f = log10 L_f^dn(varfreq[2]) - log10 L_f^std(varfreq[1]) of every family (k_vdn_brent's factors, pass 1 and pass 0),
@@ -542,16 +628,14 @@ __device__ __forceinline__ int vdn_pick3(const int* g, int s) { return s == 0 ? 
 // nine terms in (a, b) order.  Barriers between the stages.  Sums and rankings are k_fam_dnlr's fixed trees: no atomics.
 template <int T>
 __global__ void __launch_bounds__(T) k_vdn_who(DevArgs A, VdnArgs V, VdnWhoArgs W) {
-  constexpr int NW = T / 64;
   __shared__ double s_lk[256];
   __shared__ double s_tba[27], s_tdn[27], s_m3[9];
   __shared__ double s_red[2][4];
   __shared__ int s_redf[2][4];
   for (int i = threadIdx.x; i < 256; i += T) s_lk[i] = A.lktab[i];
   if (threadIdx.x < 27) s_tba[threadIdx.x] = c_TBA[0][threadIdx.x];
-  const int rows = A.counts[10], nf = A.n_fam, nk = W.n_nuc + W.n_es;
+  const int rows = A.counts[10], nf = A.n_fam;
   const size_t np = (size_t)A.n_person;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   double* ws = V.ws + (size_t)blockIdx.x * A.ws_per_lane * T + threadIdx.x;
   double* jb = W.jbuf + (size_t)blockIdx.x * W.n_es * 13;
   int par = 0;
@@ -563,25 +647,17 @@ __global__ void __launch_bounds__(T) k_vdn_who(DevArgs A, VdnArgs V, VdnWhoArgs 
     const int gidx[3] = {d_gi(a1, a1), d_gi(a1, a2), d_gi(a2, a2)};
     const uint8_t* pl = A.pl + (size_t)site * np * 10;
     const double xN = R->varfreq[2], xD = R->varfreq[1];
-    __syncthreads();   // (the previous row no longer reads the tables, the lines or jbuf)
-    if (threadIdx.x < 9) s_m3[threadIdx.x] = A.M[vdn_pick3(gidx, threadIdx.x / 3) * 10 + vdn_pick3(gidx, threadIdx.x % 3)];
-    __syncthreads();
-    if (threadIdx.x < 27) {
-      const int ij = threadIdx.x / 3, k = threadIdx.x % 3;
-      double s = 0.0;
-      for (int m = 0; m < 3; m++) s += s_tba[ij * 3 + m] * s_m3[m * 3 + k];
-      s_tdn[threadIdx.x] = s;
-    }
-    __syncthreads();
+    vdn_tables<false>(gidx, a1, a2, A.M, nullptr, s_tba, s_m3, nullptr, s_tdn);
     double ppN[9];
     d_parent_prior(PR_AUTO, xN, ppN);
     if (W.fam_k > 0) {
       double ppD[9];
       d_parent_prior(PR_AUTO, xD, ppD);
       double* line = W.fam_all ? W.fam_all + (size_t)row * nf : W.fam_line + (size_t)blockIdx.x * nf;
+      const auto term_fam = [&](int q) { return vdn_term_fam(A, V.terms, V.n_peel + V.n_nuc, W, q); };
       double part = 0.0;
       for (int q = threadIdx.x; q < V.n_terms; q += T) {
-        const int f = vdn_term_fam(A, V, W, q);
+        const int f = term_fam(q);
         if (f < 0) continue;
         const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0;
         double l_dn, l_std;
@@ -591,19 +667,10 @@ __global__ void __launch_bounds__(T) k_vdn_who(DevArgs A, VdnArgs V, VdnWhoArgs 
         } else if (q < V.n_peel + V.n_nuc) {
           l_dn = log10(vdn_nuc_lk<true>(pl + p0, np, n, gidx, s_lk, s_m3, ppN));
           l_std = log10(vdn_nuc_lk<false>(pl + p0, np, n, gidx, s_lk, s_m3, ppD));
-        } else {   // founders only: the product of lkSinglePerson, the same form in both models
-          double mN = 1.0, mD = 1.0;
-          int eN = 0, eD = 0;
-          const double gN = 1 - xN, gD = 1 - xD;
-          for (int j = 0; j < n; j++) {
-            const uint8_t* P = pl + p0 + j;
-            const double l11 = s_lk[P[gidx[0] * np]], l12 = s_lk[P[gidx[1] * np]], l22 = s_lk[P[gidx[2] * np]];
-            int e1;
-            mN = frexp(mN * (l11 * (xN * xN) + l12 * (2 * xN * gN) + l22 * (gN * gN)), &e1);
-            eN += e1;
-            mD = frexp(mD * (l11 * (xD * xD) + l12 * (2 * xD * gD) + l22 * (gD * gD)), &e1);
-            eD += e1;
-          }
+        } else {
+          double mN, mD;
+          int eN, eD;
+          vdn_founders_lk<false>(A, f, pl, s_lk, gidx, xN, xD, mN, eN, mD, eD);
           l_dn = vdn_log10_me(mN, eN);
           l_std = vdn_log10_me(mD, eD);
         }
@@ -611,59 +678,11 @@ __global__ void __launch_bounds__(T) k_vdn_who(DevArgs A, VdnArgs V, VdnWhoArgs 
         line[f] = D;
         part += D;
       }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-      if (lane == 0) s_red[par][wv] = part;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        double s = s_red[par][0];
-#pragma unroll
-        for (int w = 1; w < NW; w++) s += s_red[par][w];
-        W.fam_sum[row] = s;
-      }
-      par ^= 1;
-      double prev_lr = 0.0;
-      int prev_f = -1;
-      for (int k = 0; k < W.fam_k; k++) {   // round k takes the best entry that comes after round k - 1's in the order
-        double bl = 0.0;
-        int bf = INT_MAX;
-        for (int q = threadIdx.x; q < V.n_terms; q += T) {
-          const int f = vdn_term_fam(A, V, W, q);
-          if (f < 0) continue;
-          const double d = line[f];   // (written by this thread above)
-          const bool after = k == 0 ? d == d : (d < prev_lr || (d == prev_lr && f > prev_f));
-          if (after && fam_lr_before(d, f, bl, bf)) { bl = d; bf = f; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const double ol = __shfl_xor(bl, o, 64);
-          const int of = __shfl_xor(bf, o, 64);
-          if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
-        }
-        if (lane == 0) { s_red[par][wv] = bl; s_redf[par][wv] = bf; }
-        __syncthreads();
-        bl = s_red[par][0]; bf = s_redf[par][0];
-#pragma unroll
-        for (int w = 1; w < NW; w++)
-          if (fam_lr_before(s_red[par][w], s_redf[par][w], bl, bf)) { bl = s_red[par][w]; bf = s_redf[par][w]; }
-        par ^= 1;
-        if (threadIdx.x == 0) {
-          pm_fam_lr o;
-          o.fam = bf == INT_MAX ? -1 : bf; o.pad = 0; o.lr = bf == INT_MAX ? 0.0 : bl;
-          W.fam_top[(size_t)row * W.fam_k + k] = o;
-        }
-        if (bf == INT_MAX) { prev_lr = -INFINITY; prev_f = INT_MAX; }   // exhausted: every later round is empty too
-        else { prev_lr = bl; prev_f = bf; }
-      }
+      vdn_rank_fams<T>(W, row, line, part, V.n_terms, s_red, s_redf, par, term_fam);
     }
     if (W.car_k > 0) {
       pm_person_dn* line = W.car_all ? W.car_all + (size_t)row * np : W.car_line + (size_t)blockIdx.x * np;
-      for (int p = threadIdx.x; p < (int)np; p += T)   // founders (and anyone without both parents): no value
-        if (!W.is_kid[p]) {
-          pm_person_dn o;
-          o.person = p; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
-          line[p] = o;
-        }
+      vdn_clear_nonkids<T>(W, line, (int)np);
       // ---- closed-form nuclear families: one child per lane
       for (int ci = threadIdx.x; ci < W.n_nuc; ci += T) {
         const int2 kd = W.kids[ci];
@@ -738,9 +757,10 @@ __global__ void __launch_bounds__(T) k_vdn_who(DevArgs A, VdnArgs V, VdnWhoArgs 
       }
       // ---- peeled families: clamped peels
       if (W.n_es > 0) {   // (block-uniform)
+        const int2* kids = W.kids + W.n_nuc;
         for (int it = threadIdx.x; it < W.n_es * 9; it += T) {   // stage A
           const int ci = it / 9, k = it % 9;
-          const int2 kd = W.kids[W.n_nuc + ci];
+          const int2 kd = kids[ci];
           const int p0 = A.fam_start[kd.x], jc = kd.y, fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
           const int nonm = 7 & ~d_mend3(k);
           double J = 0.0;
@@ -749,115 +769,17 @@ __global__ void __launch_bounds__(T) k_vdn_who(DevArgs A, VdnArgs V, VdnWhoArgs 
           jb[it] = J;
         }
         __syncthreads();
-        double* jb2 = jb + (size_t)W.n_es * 9;
-        for (int it = threadIdx.x; it < W.n_es * 4; it += T) {   // stage B
-          const int ci = it / 4, slot = it % 4;
-          const int2 kd = W.kids[W.n_nuc + ci];
-          const int p0 = A.fam_start[kd.x], jc = kd.y, fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
-          double v = -1.0;
-          if (slot == 3) v = d_es_lk3_vdn(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tba, ws, T);
-          else {
-            double bj = 0.0;
-            int bi = -1;
-            for (int q = 0; q < 9; q++) { const double J = jb[ci * 9 + q]; if (J > bj) { bj = J; bi = q; } }
-            if (bi >= 0 && !((d_mend3(bi) >> slot) & 1))
-              v = d_es_lk3_vdn<true>(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tba, ws, T, fa, 1 << (bi / 3), mo, 1 << (bi % 3), jc, 1 << slot);
-          }
-          jb2[it] = v;
-        }
+        vdn_stage_b<T, false>(A, kids, W.n_es, pl, s_lk, gidx, xN, s_tdn, s_tba, ws, jb);
         __syncthreads();
-        for (int ci = threadIdx.x; ci < W.n_es; ci += T) {   // stage C
-          const int2 kd = W.kids[W.n_nuc + ci];
-          const int p = A.fam_start[kd.x] + kd.y;
-          double num = 0.0, bj = 0.0;
-          int bi = -1;
-          for (int q = 0; q < 9; q++) { const double J = jb[ci * 9 + q]; num += J; if (J > bj) { bj = J; bi = q; } }
-          const double L = jb2[ci * 4 + 3];
-          double bv = 0.0;
-          int bs = -1;
-          for (int s = 0; s < 3; s++) { const double v = jb2[ci * 4 + s]; if (v > bv) { bv = v; bs = s; } }
-          pm_person_dn o;
-          o.person = p; o.pad = 0;
-          o.fa_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bi / 3)); o.mo_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bi % 3));
-          o.kid_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bs));
-          o.pp = L > 0.0 ? fmin(num / L, 1.0) : 0.0;   // (L_f and the terms come from separate peels: rounding may pass 1)
-          line[p] = o;
-        }
+        vdn_stage_c<T>(A, kids, W.n_es, gidx, jb, line);
       }
       __syncthreads();   // the row's entries are visible to the block: the ranking reads what other threads wrote
-      double prev_pp = 0.0;
-      int prev_p = -1;
-      for (int k = 0; k < W.car_k; k++) {
-        double bl = 0.0;
-        int bf = INT_MAX;
-        for (int i = threadIdx.x; i < nk; i += T) {
-          const int2 kd = W.kids[i];
-          const int p = A.fam_start[kd.x] + kd.y;
-          const double d = line[p].pp;
-          const bool after = k == 0 ? d == d : (d < prev_pp || (d == prev_pp && p > prev_p));
-          if (after && fam_lr_before(d, p, bl, bf)) { bl = d; bf = p; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const double ol = __shfl_xor(bl, o, 64);
-          const int of = __shfl_xor(bf, o, 64);
-          if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
-        }
-        if (lane == 0) { s_red[par][wv] = bl; s_redf[par][wv] = bf; }
-        __syncthreads();
-        bl = s_red[par][0]; bf = s_redf[par][0];
-#pragma unroll
-        for (int w = 1; w < NW; w++)
-          if (fam_lr_before(s_red[par][w], s_redf[par][w], bl, bf)) { bl = s_red[par][w]; bf = s_redf[par][w]; }
-        par ^= 1;
-        if (threadIdx.x == 0) {
-          pm_person_dn o;
-          o.person = -1; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
-          if (bf != INT_MAX) o = line[bf];
-          W.car_top[(size_t)row * W.car_k + k] = o;
-        }
-        if (bf == INT_MAX) { prev_pp = -INFINITY; prev_p = INT_MAX; }   // exhausted: every later round is empty too
-        else { prev_pp = bl; prev_p = bf; }
-      }
+      vdn_rank_kids<T>(A, W, row, line, s_red, s_redf, par);
     }
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// The same on chrX (pm_engine_set_vcf_denovo_chrx_detail): the families and the children behind each DQ of a PM_CHR_X
-// section, in the sex-aware model of k_vdn_brent_x.
-
-// NonMendX(a, b, sex): the states a child of that sex can carry (a son 0 and 2, anyone else all three) that the plain
-// transmission from parents in states (a, b) gives probability 0, as a 3-bit mask.  tpl: [0..26] to a daughter, [27..53]
-// to a son.  Empty for a son of a heterozygous mother.
-__device__ __forceinline__ int vdnx_nonmend(const double* tpl, int k, bool male) {
-  const double* t = tpl + (male ? 27 : 0) + k * 3;
-  int m = 0;
-#pragma unroll
-  for (int s = 0; s < 3; s++)
-    if (!(male && s == 1) && t[s] == 0.0) m |= 1 << s;
-  return m;
-}
-
-// one round of k_vdn_who's ranking: the block's best (value, index) by fam_lr_before, the same fixed tree
-template <int T>
-__device__ __forceinline__ void vdnx_best(double& bl, int& bf, double (*red)[4], int (*redf)[4], int& par) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ol = __shfl_xor(bl, o, 64);
-    const int of = __shfl_xor(bf, o, 64);
-    if (fam_lr_before(ol, of, bl, bf)) { bl = ol; bf = of; }
-  }
-  if ((threadIdx.x & 63) == 0) { red[par][threadIdx.x >> 6] = bl; redf[par][threadIdx.x >> 6] = bf; }
-  __syncthreads();
-  bl = red[par][0]; bf = redf[par][0];
-#pragma unroll
-  for (int w = 1; w < T / 64; w++)
-    if (fam_lr_before(red[par][w], redf[par][w], bl, bf)) { bl = red[par][w]; bf = redf[par][w]; }
-  par ^= 1;
-}
-
-// k_vdn_who_x: per row of a chrX section, in the three states of the record's (ref, alt) and the model of k_vdn_brent_x,
+// k_vdn_who_x: the same per row of a chrX section, in the sex-aware model of k_vdn_brent_x,
 //   D_f = log10 L_f^dn(varfreq[2]) - log10 L_f^std(varfreq[1]) of every family (k_vdn_brent_x's factors, pass 1 and pass 0),
 //   pp_c = Sum_{a in {0,2}, b} J_c(a, b, NonMendX(a, b, sex_c)) / L_f^dn and the event of every non-founder c,
 // and their top-k rankings.  One block of T threads per row at a time, after k_finalize_vdn on the engine's stream (the
@@ -865,10 +787,8 @@ __device__ __forceinline__ void vdnx_best(double& bl, int& bf, double (*red)[4],
 // peeled, there is no closed form on X; W.n_nuc is 0): k_vdn_who's stages A, B and C with barriers between them.  A father
 // has no state 1, so stage A deals out six items per child, not nine, and writes the other three as exact zeros; a son of
 // a heterozygous mother has no non-Mendelian state, that pair gives 0 without a peel.
-// Sums and rankings are k_vdn_who's fixed trees: no atomics.
 template <int T>
 __global__ void __launch_bounds__(T) k_vdn_who_x(DevArgs A, VdnXArgs V, VdnWhoArgs W) {
-  constexpr int NW = T / 64;
   __shared__ double s_lk[256];
   __shared__ double s_tpl[54], s_tdn[54], s_m3[9], s_h3[9];   // [0..26] to a daughter, [27..53] to a son
   __shared__ double s_red[2][4];
@@ -877,7 +797,6 @@ __global__ void __launch_bounds__(T) k_vdn_who_x(DevArgs A, VdnXArgs V, VdnWhoAr
   if (threadIdx.x < 54) s_tpl[threadIdx.x] = c_TBA[1 + threadIdx.x / 27][threadIdx.x % 27];
   const int rows = A.counts[10], nf = A.n_fam, nk = W.n_es;
   const size_t np = (size_t)A.n_person;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   double* ws = V.ws + (size_t)blockIdx.x * A.ws_per_lane * T + threadIdx.x;
   double* jb = W.jbuf + (size_t)blockIdx.x * nk * 13;
   int par = 0;
@@ -889,49 +808,22 @@ __global__ void __launch_bounds__(T) k_vdn_who_x(DevArgs A, VdnXArgs V, VdnWhoAr
     const int gidx[3] = {d_gi(a1, a1), d_gi(a1, a2), d_gi(a2, a2)};
     const uint8_t* pl = A.pl + (size_t)site * np * 10;
     const double xN = R->varfreq[2], xD = R->varfreq[1];
-    __syncthreads();   // (the previous row no longer reads the tables, the lines or jbuf; s_tpl is written)
-    if (threadIdx.x < 9) {
-      const int x = threadIdx.x / 3, y = threadIdx.x % 3;
-      s_m3[threadIdx.x] = A.M[vdn_pick3(gidx, x) * 10 + vdn_pick3(gidx, y)];
-      s_h3[threadIdx.x] = (x == 1 || y == 1) ? 0.0 : V.a4[(((x ? a2 : a1) - 1) & 3) * 4 + (((y ? a2 : a1) - 1) & 3)];   // (bases are 1..4)
-    }
-    __syncthreads();
-    if (threadIdx.x < 54) {
-      const int ij = (threadIdx.x % 27) / 3, k = threadIdx.x % 3;
-      const double* tp = s_tpl + (threadIdx.x < 27 ? 0 : 27);
-      const double* mm = threadIdx.x < 27 ? s_m3 : s_h3;
-      double s = 0.0;
-      for (int m = 0; m < 3; m++) s += tp[ij * 3 + m] * mm[m * 3 + k];
-      s_tdn[threadIdx.x] = s;
-    }
-    __syncthreads();
+    vdn_tables<true>(gidx, a1, a2, A.M, V.a4, s_tpl, s_m3, s_h3, s_tdn);
     if (W.fam_k > 0) {
       double* line = W.fam_all ? W.fam_all + (size_t)row * nf : W.fam_line + (size_t)blockIdx.x * nf;
+      const auto term_fam = [&](int q) { return vdn_term_fam(A, V.terms, V.n_peel, W, q); };
       double part = 0.0;
       for (int q = threadIdx.x; q < V.n_terms; q += T) {
-        const int x = V.terms[q];
-        int f = x;
+        const int f = term_fam(q);
+        if (f < 0) continue;
         double l_dn, l_std;
         if (q < V.n_peel) {
-          l_dn = log10(d_es_lk3_vdn_x(A, f, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, T));
-          l_std = log10(d_es_lk3_vdn_x(A, f, pl, s_lk, gidx, xD, s_tpl, s_tpl, ws, T));
-        } else {   // founders only: the family's first person carries the product over its persons, in person order
-          f = W.pfam[x];
-          const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0;
-          if (x != p0) continue;
-          double mN = 1.0, mD = 1.0;
-          int eN = 0, eD = 0;
-          const double gN = 1 - xN, gD = 1 - xD;
-          for (int j = 0; j < n; j++) {
-            const uint8_t* P = pl + p0 + j;
-            const double l11 = s_lk[P[gidx[0] * np]], l12 = s_lk[P[gidx[1] * np]], l22 = s_lk[P[gidx[2] * np]];
-            const bool male = A.sex[p0 + j] == MALE;   // lkSinglePerson: a male is hemizygous
-            int e1;
-            mN = frexp(mN * (male ? l11 * xN + l22 * gN : l11 * (xN * xN) + l12 * (2 * xN * gN) + l22 * (gN * gN)), &e1);
-            eN += e1;
-            mD = frexp(mD * (male ? l11 * xD + l22 * gD : l11 * (xD * xD) + l12 * (2 * xD * gD) + l22 * (gD * gD)), &e1);
-            eD += e1;
-          }
+          l_dn = log10(d_es_lk3_vdn<false, true>(A, f, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, T));
+          l_std = log10(d_es_lk3_vdn<false, true>(A, f, pl, s_lk, gidx, xD, s_tpl, s_tpl, ws, T));
+        } else {
+          double mN, mD;
+          int eN, eD;
+          vdn_founders_lk<true>(A, f, pl, s_lk, gidx, xN, xD, mN, eN, mD, eD);
           l_dn = vdn_log10_me(mN, eN);
           l_std = vdn_log10_me(mD, eD);
         }
@@ -939,51 +831,11 @@ __global__ void __launch_bounds__(T) k_vdn_who_x(DevArgs A, VdnXArgs V, VdnWhoAr
         line[f] = D;
         part += D;
       }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-      if (lane == 0) s_red[par][wv] = part;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        double s = s_red[par][0];
-#pragma unroll
-        for (int w = 1; w < NW; w++) s += s_red[par][w];
-        W.fam_sum[row] = s;
-      }
-      par ^= 1;
-      double prev_lr = 0.0;
-      int prev_f = -1;
-      for (int k = 0; k < W.fam_k; k++) {   // round k takes the best entry that comes after round k - 1's in the order
-        double bl = 0.0;
-        int bf = INT_MAX;
-        for (int q = threadIdx.x; q < V.n_terms; q += T) {
-          const int x = V.terms[q];
-          int f = x;
-          if (q >= V.n_peel) {
-            f = W.pfam[x];
-            if (x != A.fam_start[f]) continue;
-          }
-          const double d = line[f];   // (written by this thread above)
-          const bool after = k == 0 ? d == d : (d < prev_lr || (d == prev_lr && f > prev_f));
-          if (after && fam_lr_before(d, f, bl, bf)) { bl = d; bf = f; }
-        }
-        vdnx_best<T>(bl, bf, s_red, s_redf, par);
-        if (threadIdx.x == 0) {
-          pm_fam_lr o;
-          o.fam = bf == INT_MAX ? -1 : bf; o.pad = 0; o.lr = bf == INT_MAX ? 0.0 : bl;
-          W.fam_top[(size_t)row * W.fam_k + k] = o;
-        }
-        if (bf == INT_MAX) { prev_lr = -INFINITY; prev_f = INT_MAX; }   // exhausted: every later round is empty too
-        else { prev_lr = bl; prev_f = bf; }
-      }
+      vdn_rank_fams<T>(W, row, line, part, V.n_terms, s_red, s_redf, par, term_fam);
     }
     if (W.car_k > 0) {
       pm_person_dn* line = W.car_all ? W.car_all + (size_t)row * np : W.car_line + (size_t)blockIdx.x * np;
-      for (int p = threadIdx.x; p < (int)np; p += T)   // founders (and anyone without both parents): no value
-        if (!W.is_kid[p]) {
-          pm_person_dn o;
-          o.person = p; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
-          line[p] = o;
-        }
+      vdn_clear_nonkids<T>(W, line, (int)np);
       if (nk > 0) {   // (block-uniform)
         for (int it = threadIdx.x; it < nk * 6; it += T) {   // stage A: the six pairs of a father in state 0 or 2
           const int ci = it / 6, b = it % 3, k = (it % 6 < 3 ? 0 : 6) + b;
@@ -992,69 +844,17 @@ __global__ void __launch_bounds__(T) k_vdn_who_x(DevArgs A, VdnXArgs V, VdnWhoAr
           const int nonm = vdnx_nonmend(s_tpl, k, A.sex[p0 + jc] == MALE);
           double J = 0.0;
           if (nonm)
-            J = d_es_lk3_vdn_x<true>(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, T, fa, 1 << (k / 3), mo, 1 << b, jc, nonm);
+            J = d_es_lk3_vdn<true, true>(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, T, fa, 1 << (k / 3), mo, 1 << b, jc, nonm);
           jb[ci * 9 + k] = J;
           if (k < 3) jb[ci * 9 + 3 + b] = 0.0;   // a father has no state 1: exactly 0, no peel
         }
         __syncthreads();
-        double* jb2 = jb + (size_t)nk * 9;
-        for (int it = threadIdx.x; it < nk * 4; it += T) {   // stage B
-          const int ci = it / 4, slot = it % 4;
-          const int2 kd = W.kids[ci];
-          const int p0 = A.fam_start[kd.x], jc = kd.y, fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
-          double v = -1.0;
-          if (slot == 3) v = d_es_lk3_vdn_x(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, T);
-          else {
-            double bj = 0.0;
-            int bi = -1;
-            for (int q = 0; q < 9; q++) { const double J = jb[ci * 9 + q]; if (J > bj) { bj = J; bi = q; } }
-            if (bi >= 0 && ((vdnx_nonmend(s_tpl, bi, A.sex[p0 + jc] == MALE) >> slot) & 1))
-              v = d_es_lk3_vdn_x<true>(A, kd.x, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, T, fa, 1 << (bi / 3), mo, 1 << (bi % 3), jc, 1 << slot);
-          }
-          jb2[it] = v;
-        }
+        vdn_stage_b<T, true>(A, W.kids, nk, pl, s_lk, gidx, xN, s_tdn, s_tpl, ws, jb);
         __syncthreads();
-        for (int ci = threadIdx.x; ci < nk; ci += T) {   // stage C
-          const int2 kd = W.kids[ci];
-          const int p = A.fam_start[kd.x] + kd.y;
-          double num = 0.0, bj = 0.0;
-          int bi = -1;
-          for (int q = 0; q < 9; q++) { const double J = jb[ci * 9 + q]; num += J; if (J > bj) { bj = J; bi = q; } }
-          const double L = jb2[ci * 4 + 3];
-          double bv = 0.0;
-          int bs = -1;
-          for (int s = 0; s < 3; s++) { const double v = jb2[ci * 4 + s]; if (v > bv) { bv = v; bs = s; } }
-          pm_person_dn o;
-          o.person = p; o.pad = 0;
-          o.fa_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bi / 3)); o.mo_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bi % 3));
-          o.kid_g = (int8_t)(bs < 0 ? -1 : vdn_pick3(gidx, bs));
-          o.pp = L > 0.0 ? fmin(num / L, 1.0) : 0.0;   // (L_f and the terms come from separate peels: rounding may pass 1)
-          line[p] = o;
-        }
+        vdn_stage_c<T>(A, W.kids, nk, gidx, jb, line);
       }
       __syncthreads();   // the row's entries are visible to the block: the ranking reads what other threads wrote
-      double prev_pp = 0.0;
-      int prev_p = -1;
-      for (int k = 0; k < W.car_k; k++) {
-        double bl = 0.0;
-        int bf = INT_MAX;
-        for (int i = threadIdx.x; i < nk; i += T) {
-          const int2 kd = W.kids[i];
-          const int p = A.fam_start[kd.x] + kd.y;
-          const double d = line[p].pp;
-          const bool after = k == 0 ? d == d : (d < prev_pp || (d == prev_pp && p > prev_p));
-          if (after && fam_lr_before(d, p, bl, bf)) { bl = d; bf = p; }
-        }
-        vdnx_best<T>(bl, bf, s_red, s_redf, par);
-        if (threadIdx.x == 0) {
-          pm_person_dn o;
-          o.person = -1; o.fa_g = o.mo_g = o.kid_g = -1; o.pad = 0; o.pp = 0.0;
-          if (bf != INT_MAX) o = line[bf];
-          W.car_top[(size_t)row * W.car_k + k] = o;
-        }
-        if (bf == INT_MAX) { prev_pp = -INFINITY; prev_p = INT_MAX; }   // exhausted: every later round is empty too
-        else { prev_pp = bl; prev_p = bf; }
-      }
+      vdn_rank_kids<T>(A, W, row, line, s_red, s_redf, par);
     }
   }
 }
