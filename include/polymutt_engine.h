@@ -492,6 +492,38 @@ int pm_engine_set_vcf_posteriors(pm_engine *eng, int32_t on);
  * batch returned.  PM_EINVAL: the feature is off, or a submitted batch has not been collected. */
 int pm_engine_vcf_posteriors(pm_engine *eng, int32_t *n_rows, pm_vcf_post *out);
 
+/* Transmission phase of every non-founder of every written record of a vcf_mode batch (additive to ABI 8: callers
+ * detect the feature by this symbol; the reference has no counterpart).  With (a1, a2) = (ref, alt) and the states
+ * 0, 1, 2 = a1a1, a1a2, a2a2, for a non-founder c whose father and mother are in its family
+ *   p12 = P(c got a1 from the father and a2 from the mother | data)
+ *       = [J(0,1,1) + J(0,2,1) + J(1,2,1) + J(1,1,1) / 2] / L
+ *   p21 = P(c got a2 from the father and a1 from the mother | data)
+ *       = [J(1,0,1) + J(2,0,1) + J(2,1,1) + J(1,1,1) / 2] / L
+ * where J(a, b, s) is the family likelihood restricted to father = a, mother = b, child = s under the plain transmission
+ * and L the unrestricted one, at the site's frequency (pm_site_result.af) with the founder priors, the single-family
+ * prior mode and the family routing of the genotype rows and of pm_vcf_post: p12 + p21 is that plane's p[1] up to the
+ * order of the sums.  Each value is the double quotient rounded once to float.  Founders, persons whose normalising sum
+ * is zero and every person of a chrX / chrY / MT section are (0, 0): sex-aware phase is not computed. */
+typedef struct {
+  float p12, p21;              /* P(paternal a1 | maternal a2), P(paternal a2 | maternal a1) given the pedigree */
+} pm_vcf_phase;
+
+/* Switch the phase plane on or off (off at creation).  With it on, every batch runs one extra pass after the standard
+ * posterior stage and the posterior plane's (k_vcf_phase_lean / k_vcf_phase_nuc / k_vcf_phase_es, chosen as that
+ * stage's kernels are), which writes only the plane: the site results, the genotype rows, the posterior plane and the
+ * de novo outputs are those of the engine without it, byte for byte.  The device buffer is max_batch x n_person x 8
+ * bytes, allocated on the first `on` and freed on `off` or pm_engine_destroy; off = nothing allocated, nothing
+ * launched.  Independent of pm_engine_set_vcf_posteriors and of the pm_engine_set_vcf_denovo family: either may be on
+ * without the other and neither switches the other off.  It may be set at any point between batches.  PM_EINVAL: an
+ * engine without vcf_mode, or a submitted batch not yet collected. */
+int pm_engine_set_vcf_phase(pm_engine *eng, int32_t on);
+
+/* The plane of the last finished batch (pm_engine_run, pm_engine_run_vcf or pm_engine_submit / pm_engine_collect):
+ * *n_rows = the batch's row count, out[row * n_person + person] with the rows of pm_site_result.call_row and the
+ * persons in pm_pedigree order.  out may be NULL (the count alone).  After PM_EBRENT: the same prefix of rows the
+ * batch returned.  PM_EINVAL: the feature is off, or a submitted batch has not been collected. */
+int pm_engine_vcf_phase(pm_engine *eng, int32_t *n_rows, pm_vcf_phase *out);
+
 /* Page-locked host memory for pm_engine_submit's inputs and the result rows (H2D/D2H at full PCIe rate). */
 int pm_host_alloc(uint64_t bytes, void **h_ptr);
 int pm_host_free(void *h_ptr);

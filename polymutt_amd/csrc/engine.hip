@@ -7,6 +7,7 @@
 #include "brent_variants.h"
 #include "vcf_denovo_dev.h"
 #include "vcf_post_dev.h"
+#include "vcf_phase_dev.h"
 
 #define PM_BRENT_X(part, ...) extern template __global__ void k_brent<__VA_ARGS__>(DevArgs, int);
 PM_BRENT_VARIANTS
@@ -161,6 +162,11 @@ struct pm_engine {
   // the genotype posterior plane of vcf_mode batches (pm_engine_set_vcf_posteriors): off = no buffer, no launch
   bool vp_on = false, vp_valid = false;   // vp_valid: the last finished batch filled the plane
   pm_vcf_post* d_vp = nullptr;            // [max_batch][n_person]
+  // the transmission phase plane of vcf_mode batches (pm_engine_set_vcf_phase): off = no buffer, no launch
+  bool vph_on = false, vph_valid = false;   // vph_valid: the last finished batch filled the plane
+  pm_vcf_phase* d_vph = nullptr;            // [max_batch][n_person]
+  int* d_vph_kids[2] = {nullptr, nullptr};  // (family << 8 | member) of the non-founders of peeled families: plan 0 / plan 1
+  std::vector<int> vph_kids_h[2];
   std::vector<int> fam_kind_h, fam_perm_h;
   std::vector<int32_t> fa_h, mo_h;  // family-local parent indices (-1: none)
   unsigned long long* d_counters = nullptr;
@@ -384,7 +390,7 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf,
                   E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws, E->d_vdnx_terms, E->d_vdnx_ws, E->d_vw_row_site, E->d_vw_pfam, E->d_vw_fam_top, E->d_vw_fam_sum,
                   E->d_vw_fam_all, E->d_vw_fam_line, E->d_vw_car_top, E->d_vw_car_all, E->d_vw_car_line, E->d_vw_kids, E->d_vw_is_kid,
-                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf, E->d_vp};
+                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf, E->d_vp, E->d_vph, E->d_vph_kids[0], E->d_vph_kids[1]};
   for (void* b : bufs) if (b) hipFree(b);
   for (auto& pl : E->d_jit_slots)
     for (int* b : pl) if (b) hipFree(b);
@@ -609,6 +615,12 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
           if (ped->fam_kind[f] != PM_FAM_FOUNDERS) e1.push_back(f << 8 | j);
         }
       }
+      // ... and their non-founders, both parents in the family (k_vcf_phase_es; uploaded by pm_engine_set_vcf_phase)
+      for (int plan = 0; plan < 2; plan++)
+        for (int e : plan ? e1 : e0) {
+          const int p = ped->fam_start[e >> 8] + (e & 255), n = ped->fam_start[(e >> 8) + 1] - ped->fam_start[e >> 8];
+          if (!ped->is_founder[p] && fa[p] >= 0 && mo[p] >= 0 && fa[p] < n && mo[p] < n && fa[p] != mo[p]) E->vph_kids_h[plan].push_back(e);
+        }
       E->n_es_pers = (int)e0.size();
       E->n_es_pers1 = (int)e1.size();
       DALLOC(E->d_es_pers, std::max<size_t>(1, e0.size()));
@@ -1215,6 +1227,36 @@ static int launch_vcf_posteriors(pm_engine* E, const DevArgs& A, bool lean, bool
   return PM_OK;
 }
 
+// The transmission phase plane of a vcf_mode batch's rows (vcf_phase_dev.h): one more pass behind the standard posterior
+// stage and the posterior plane's, with launch_vcf_posteriors' choice of kernels and launch shapes.  Sections that are not
+// autosomal have no phase: their plane is cleared instead.
+static int launch_vcf_phase(pm_engine* E, const DevArgs& A, bool lean, bool es) {
+  E->vph_valid = true;
+  if (E->chrom != PM_CHR_AUTO) {
+    HIP_TRY(hipMemsetAsync(E->d_vph, 0, sizeof(pm_vcf_phase) * (size_t)E->max_batch * E->n_person, E->stream));
+    return PM_OK;
+  }
+  const int plan = E->use_plan1 ? 1 : 0;
+  VphArgs P;
+  P.phase = E->d_vph; P.kids = E->d_vph_kids[plan]; P.n_kids = (int)E->vph_kids_h[plan].size();
+  if (lean) hipLaunchKernelGGL(k_vcf_phase_lean, dim3(E->grid_post), dim3(256), (size_t)E->n_fam * 5, E->stream, A, P);
+  else hipLaunchKernelGGL(k_vcf_phase_nuc, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
+  HIP_TRY(hipGetLastError());
+  if (es && P.n_kids > 0) {   // k_posterior_es's choice between the LDS and the HBM workspace
+    const size_t per = (size_t)E->ws_per_lane * sizeof(double);
+    int bt = 0;
+    for (int t : {256, 128, 64})
+      if (!bt && per * t <= 64 * 1024 && !E->sw.es_post_hbm) bt = t;
+    if (bt) {
+      const int per_cu = std::max(1, (int)((160 * 1024) / (per * bt + 3 * 1024)));
+      hipLaunchKernelGGL(k_vcf_phase_es<true>, dim3(E->n_cu * per_cu * 2), dim3(bt), per * bt, E->stream, A, P);
+    } else
+      hipLaunchKernelGGL(k_vcf_phase_es<false>, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
+    HIP_TRY(hipGetLastError());
+  }
+  return PM_OK;
+}
+
 static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* dm, const uint8_t* ref, pm_site_result* res,
                         pm_geno_call* calls) {
   DevArgs A = make_args(E, n, pl, dm, ref, res, calls);
@@ -1323,6 +1365,10 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
     if (E->vp_on) {
       HIP_TRY(hipGetLastError());
       if ((rc = launch_vcf_posteriors(E, A, lean, es))) return rc;
+    }
+    if (E->vph_on) {
+      HIP_TRY(hipGetLastError());
+      if ((rc = launch_vcf_phase(E, A, lean, es))) return rc;
     }
   }
   HIP_TRY(hipGetLastError());
@@ -1546,6 +1592,48 @@ int pm_engine_vcf_posteriors(pm_engine* E, int32_t* n_rows, pm_vcf_post* out) {
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
     HIP_TRY(hipMemcpy(out, E->d_vp, sizeof(pm_vcf_post) * (size_t)*n_rows * E->n_person, hipMemcpyDeviceToHost));
+  }
+  return PM_OK;
+}
+
+int pm_engine_set_vcf_phase(pm_engine* E, int32_t on) {
+  if (!E) { pm_set_last_error("pm_engine_set_vcf_phase: invalid arguments"); return PM_EINVAL; }
+  if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_phase: the engine was created without vcf_mode"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_vcf_phase: a submitted batch has not been collected"); return PM_EINVAL; }
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  if (!on) {
+    E->vph_on = E->vph_valid = false;
+    void** bufs[] = {(void**)&E->d_vph, (void**)&E->d_vph_kids[0], (void**)&E->d_vph_kids[1]};
+    for (void** b : bufs) {
+      if (*b) (void)hipFree(*b);
+      *b = nullptr;
+    }
+    return PM_OK;
+  }
+  if (E->vph_on) return PM_OK;   // (already on: the last batch's plane stays)
+  const size_t cells = (size_t)E->max_batch * E->n_person;   // max_batch x n_person x 8 bytes
+  if (int rc = dalloc(&E->d_vph, cells)) return rc;
+  HIP_TRY(hipMemset(E->d_vph, 0, cells * sizeof(pm_vcf_phase)));   // (the founders of peeled families are never written)
+  for (int plan = 0; plan < 2; plan++) {
+    const std::vector<int>& k = E->vph_kids_h[plan];
+    if (int rc = dalloc(&E->d_vph_kids[plan], std::max<size_t>(1, k.size()))) return rc;
+    if (!k.empty()) HIP_TRY(hipMemcpy(E->d_vph_kids[plan], k.data(), sizeof(int) * k.size(), hipMemcpyHostToDevice));
+  }
+  E->vph_on = true;
+  E->vph_valid = false;   // (no batch has filled it yet)
+  return PM_OK;
+}
+
+int pm_engine_vcf_phase(pm_engine* E, int32_t* n_rows, pm_vcf_phase* out) {
+  if (!E || !n_rows) { pm_set_last_error("pm_engine_vcf_phase: invalid arguments"); return PM_EINVAL; }
+  if (!E->vph_on) { pm_set_last_error("pm_engine_vcf_phase: the feature is off (pm_engine_set_vcf_phase)"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_vcf_phase: a submitted batch has not been collected"); return PM_EINVAL; }
+  *n_rows = E->vph_valid ? E->last_rows : 0;
+  if (out && *n_rows > 0) {
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipMemcpy(out, E->d_vph, sizeof(pm_vcf_phase) * (size_t)*n_rows * E->n_person, hipMemcpyDeviceToHost));
   }
   return PM_OK;
 }

@@ -105,6 +105,8 @@ PERSON_DN_DTYPE = np.dtype([("person", "<i4"), ("fa_g", "i1"), ("mo_g", "i1"), (
 assert PERSON_DN_DTYPE.itemsize == 16
 VCF_POST_DTYPE = np.dtype([("p", "<f4", (3,))])   # pm_vcf_post
 assert VCF_POST_DTYPE.itemsize == 12
+VCF_PHASE_DTYPE = np.dtype([("p12", "<f4"), ("p21", "<f4")])   # pm_vcf_phase
+assert VCF_PHASE_DTYPE.itemsize == 8
 
 _lib = None
 
@@ -137,6 +139,8 @@ EXPORTS = {
     "pm_engine_vcf_denovo_carriers": (i32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_engine_set_vcf_posteriors": (i32, [C.c_void_p, i32]),
     "pm_engine_vcf_posteriors": (i32, [C.c_void_p, P(i32), C.c_void_p]),
+    "pm_engine_set_vcf_phase": (i32, [C.c_void_p, i32]),
+    "pm_engine_vcf_phase": (i32, [C.c_void_p, P(i32), C.c_void_p]),
     "pm_host_alloc": (i32, [u64, P(C.c_void_p)]),
     "pm_host_free": (i32, [C.c_void_p]),
     "pm_engine_to_planar": (i32, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
@@ -504,6 +508,24 @@ class Engine:
         if n.value:
             self._check(self.lib.pm_engine_vcf_posteriors(self.h, C.byref(n), _ptr(post)))
         return post["p"].copy() if n.value else np.zeros((0, self.n_person, 3), dtype=np.float32)
+
+    def set_vcf_phase(self, on=True):
+        """pm_engine_set_vcf_phase (vcf_mode engines): every batch also keeps, for every non-founder of every written
+        row of an autosomal section, the two ordered heterozygous posteriors (paternal allele first); off (the default)
+        allocates and launches nothing.  Every other output is the same bytes either way."""
+        self._check(self.lib.pm_engine_set_vcf_phase(self.h, 1 if on else 0))
+
+    def vcf_phase(self):
+        """pm_engine_vcf_phase for the last finished batch: float32 [rows, n_person, 2] = (p12, p21), the posterior of
+        the child having the reference allele from the father and the alternative one from the mother, and the reverse;
+        rows indexed by call_row (after a stuck Brent: the rows the batch returned).  Founders are (0, 0)."""
+        n = i32(0)
+        self._check(self.lib.pm_engine_vcf_phase(self.h, C.byref(n), None))
+        if not n.value:
+            return np.zeros((0, self.n_person, 2), dtype=np.float32)
+        ph = np.zeros((n.value, self.n_person), dtype=VCF_PHASE_DTYPE)
+        self._check(self.lib.pm_engine_vcf_phase(self.h, C.byref(n), _ptr(ph)))
+        return np.stack([ph["p12"], ph["p21"]], axis=-1)
 
     def stuck_site(self):
         """pm_engine_stuck_site: the first site of the last finished batch whose Brent hit ITMAX (-1: none)."""

@@ -51,6 +51,12 @@ struct Options {
   // genotype posteriors given the pedigree behind its GT and GQ (pm_engine_set_vcf_posteriors); combines freely with the
   // --vcf_denovo flags
   bool vcf_posteriors = false;
+  // --vcf_phase (with --in_vcf): a heterozygous non-founder of an autosomal record whose transmission phase is known with
+  // a quality PQ >= --vcf_phase_minPQ (0..99, default 10) prints its GT phased, paternal allele first (0|1 or 1|0), and
+  // every sample gets a PQ sub-field before PL / GL (pm_engine_set_vcf_phase); combines freely with the other --vcf_ flags
+  bool vcf_phase = false;
+  int vcf_phase_minPQ = 10;
+  bool vcf_phase_minPQ_given = false;
   std::string cmd;
   pm_params params() const;
 };
@@ -128,6 +134,9 @@ class SiteEvaluator {
   // returns the row count (pm_engine_set_vcf_posteriors / pm_engine_vcf_posteriors)
   virtual void set_vcf_posteriors(bool on) { (void)on; throw FatalError("--vcf_posteriors is not supported by this evaluator\n"); }
   virtual int vcf_posteriors(pm_vcf_post* out) { (void)out; throw FatalError("--vcf_posteriors is not supported by this evaluator\n"); }
+  // --vcf_phase: the same pair for the transmission phase plane (pm_engine_set_vcf_phase / pm_engine_vcf_phase)
+  virtual void set_vcf_phase(bool on) { (void)on; throw FatalError("--vcf_phase is not supported by this evaluator\n"); }
+  virtual int vcf_phase(pm_vcf_phase* out) { (void)out; throw FatalError("--vcf_phase is not supported by this evaluator\n"); }
   // Host memory for the batch buffers (the engine: page-locked, for asynchronous copies)
   virtual void* host_alloc(size_t bytes);
   virtual void host_free(void* p);

@@ -252,6 +252,7 @@ struct State {            // what FamilyLikelihoodSeq_VCF holds between records 
   double qual = 0.0, min = 0.0;
   std::vector<pm_vcf_call> calls;    // per flattened person
   std::vector<pm_vcf_post> post;     // --vcf_posteriors: their posteriors (all zero before the first computed record)
+  std::vector<pm_vcf_phase> phase;   // --vcf_phase: their transmission phase (likewise)
   int a_ref = 0;                     // allele of the label convention (always allele1 in this path)
 };
 
@@ -363,6 +364,9 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       fprintf(out, "%s",
               "##FORMAT=<ID=DS,Number=1,Type=Float,Description=\"Dosage: Defined As the Expected Alternative Allele Count\">\n"
               "##FORMAT=<ID=GP,Number=G,Type=Float,Description=\"Genotype Posterior Probabilities Given the Pedigree\">\n");
+    if (opt.vcf_phase)   // (--vcf_phase: no reference counterpart)
+      fprintf(out, "%s",
+              "##FORMAT=<ID=PQ,Number=1,Type=Integer,Description=\"Phred-scaled quality of the transmission phase of GT (paternal|maternal)\">\n");
     fprintf(out, "%s",
             "##FORMAT=<ID=PL,Number=3,Type=Integer,Description=\"Phred-scaled Genotype Likelihoods\">\n"
             "##FORMAT=<ID=GL,Number=3,Type=Float,Description=\"Log10 Genotype Likelihoods\">\n");
@@ -388,6 +392,9 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     eval.set_vcf_denovo_chrx_detail(true);   // (last: the other three setters switch it off)
   const bool vp = opt.vcf_posteriors;
   if (vp) eval.set_vcf_posteriors(true);
+  const bool vph = opt.vcf_phase;
+  const int min_pq = opt.vcf_phase_minPQ;
+  if (vph) eval.set_vcf_phase(true);
   const int B = std::max(1, opt.batch);
   // Two batches: the main thread reads, classifies and parses records into one while the flusher thread runs the
   // engine on the other, formats its records and hands their text to the writer thread.  A batch's PL rows are in
@@ -403,13 +410,14 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     std::vector<pm_site_result> res;
     std::vector<Pending*> pend;
     std::vector<pm_vcf_post> post;   // --vcf_posteriors: the batch's posterior plane, fetched next to the calls
+    std::vector<pm_vcf_phase> phase; // --vcf_phase: the batch's phase plane, likewise
     int nb = 0;
-    BatchBuf(SiteEvaluator& ev, int b, int n, bool with_post)
+    BatchBuf(SiteEvaluator& ev, int b, int n, bool with_post, bool with_phase)
         : e(ev), pl((uint8_t*)ev.host_alloc((size_t)b * n * 10)), calls((pm_vcf_call*)ev.host_alloc((size_t)b * n * sizeof(pm_vcf_call))),
-          ref(b), res(b), post(with_post ? (size_t)b * n : 0) {}
+          ref(b), res(b), post(with_post ? (size_t)b * n : 0), phase(with_phase ? (size_t)b * n : 0) {}
     ~BatchBuf() { e.host_free(pl); e.host_free(calls); }
   };
-  BatchBuf bb0(eval, B, np, vp), bb1(eval, B, np, vp);
+  BatchBuf bb0(eval, B, np, vp, vph), bb1(eval, B, np, vp, vph);
   BatchBuf* const bbs[2] = {&bb0, &bb1};
   if (!bb0.pl || !bb1.pl || !bb0.calls || !bb1.calls) throw FatalError("out of host memory\n");
   int cb = 0;   // the batch the main thread fills
@@ -434,6 +442,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   State st;
   st.calls.assign(np, pm_vcf_call{0, 0, PM_LBL_VCF_DIPLOID, 0});
   if (vp) st.post.assign(np, pm_vcf_post{{0.f, 0.f, 0.f}});
+  if (vph) st.phase.assign(np, pm_vcf_phase{0.f, 0.f});
 
   // The state a record is printed with: its own (a computed record) or the previous computed record's (a record
   // without data, PedVCF.cpp:113-122): QUAL, the AF minimiser and every person's call.
@@ -447,6 +456,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     const pm_fam_lr* dnf = nullptr;
     const pm_person_dn* dnc = nullptr;
     const pm_vcf_post* post = nullptr;   // --vcf_posteriors: every person's posteriors, carried like the calls
+    const pm_vcf_phase* phase = nullptr; // --vcf_phase: every person's transmission phase, carried like the calls
   };
   auto fresh_state = [&](const Pending& r, const pm_site_result* Rs, const pm_vcf_call* C) {
     // mono/poly -> QUAL (PedVCF.cpp:136-152), with the reference's operator-precedence slip
@@ -507,7 +517,8 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       fv[s] = F;
       if (F.db >= 0) totalDepth += atoi_fast(lp + F.db);
     }
-    out.resize(L.size() + (vp ? 49 : 17) * ns + 1024);   // (--vcf_posteriors: at most 32 more characters per sample)
+    // (--vcf_posteriors: at most 32 more characters per sample; --vcf_phase: at most 3, PQ and its colon)
+    out.resize(L.size() + ((vp ? 49 : 17) + (vph ? 3 : 0)) * ns + 1024);
     char* w = &out[0];
     auto put = [&](const char* p, size_t n) { memcpy(w, p, n); w += n; };
     auto fld = [&](int k) { put(lp + r.cols[k].b, (size_t)(r.cols[k].e - r.cols[k].b)); };
@@ -525,7 +536,9 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     int hn = snprintf(head, sizeof(head), "\t%.2f\t", S.qual);
     if (hn >= (int)sizeof(head)) { putf(hn); w += snprintf(w, (size_t)hn + 1, "\t%.2f\t", S.qual); } else putf(hn);
     fld(6);
-    const char* fmt_s = vp ? (fs.PL_idx > 0 ? "GT:GQ:DP:DS:GP:PL" : "GT:GQ:DP:DS:GP:GL") : fs.PL_idx > 0 ? "GT:GQ:DP:PL" : "GT:GQ:DP:GL";
+    const bool has_pl = fs.PL_idx > 0;
+    const char* fmt_s = vp ? (vph ? (has_pl ? "GT:GQ:DP:DS:GP:PQ:PL" : "GT:GQ:DP:DS:GP:PQ:GL") : has_pl ? "GT:GQ:DP:DS:GP:PL" : "GT:GQ:DP:DS:GP:GL")
+                           : (vph ? (has_pl ? "GT:GQ:DP:PQ:PL" : "GT:GQ:DP:PQ:GL") : has_pl ? "GT:GQ:DP:PL" : "GT:GQ:DP:GL");
     std::string dq_t;
     if (S.has_dq) {
       char v[64];
@@ -565,11 +578,25 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       const pm_vcf_call& c = S.calls[inc_cols[s].second];
       const Fields& F = fv[s];
       const char* lab;
+      bool het = false;   // GT prints as 0/1
       if (c.label == PM_LBL_DOT) lab = ".";
       else if (c.gq <= 0) lab = "./.";
       else {
         const int bb = c.best < 0 || c.best > 2 ? 0 : c.best;
         lab = c.label == PM_LBL_VCF_HAPLOID ? kHap[bb] : kDip[bb];
+        het = c.label != PM_LBL_VCF_HAPLOID && bb == 1;
+      }
+      // --vcf_phase: a het sample with a phase (a non-founder of an autosomal record: everyone else's plane entry is zero)
+      // gets PQ = the Phred-scaled posterior of the less likely order, and at PQ >= --vcf_phase_minPQ its GT phased, the
+      // paternal allele first; a tie (PQ 3) prints 0|1
+      int pq = -1;
+      if (vph && het) {
+        const pm_vcf_phase& h = S.phase[inc_cols[s].second];
+        const double lo = std::min((double)h.p12, (double)h.p21), hi = std::max((double)h.p12, (double)h.p21);
+        if (lo + hi > 0) {
+          pq = lo == 0 ? 99 : std::min(99, (int)(-10.0 * log10(lo / (lo + hi)) + 0.5));
+          if (pq >= min_pq) lab = h.p12 >= h.p21 ? "0|1" : "1|0";
+        }
       }
       *w++ = '\t';
       put(lab, strlen(lab));
@@ -590,6 +617,11 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
         }
         *w++ = ':';
       }
+      if (vph) {
+        if (pq >= 0) w = put_int_buf(w, pq);
+        else *w++ = '.';
+        *w++ = ':';
+      }
       if (F.pb >= 0) put(lp + F.pb, (size_t)(F.pe - F.pb));
       else *w++ = '.';
     }
@@ -600,6 +632,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   auto write_record = [&](FILE* fo, const Pending& r) {
     RecState S{st.qual, st.min, st.calls.data()};
     S.post = st.post.data();
+    S.phase = st.phase.data();
     std::string t;
     format_record(t, r, S);
     fwrite(t.data(), 1, t.size(), fo);
@@ -658,6 +691,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
           if (pend[k]->computed && pend[k]->slot >= e.valid) { npend = k; break; }
       }
       if (vp) eval.vcf_posteriors(bb.post.data());   // (after a stuck Brent: the rows of the records that still go out)
+      if (vph) eval.vcf_phase(bb.phase.data());
     }
     // the batch's rows (the sites with DQ at or above the threshold; after a stuck Brent those before it): slot -> row
     std::vector<int32_t> row_of;
@@ -679,11 +713,13 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     states.resize(npend);
     RecState cur{st.qual, st.min, st.calls.data()};
     cur.post = st.post.data();
+    cur.phase = st.phase.data();
     for (size_t k = 0; k < npend; k++) {
       const Pending& r = *pend[k];
       if (r.computed) {
         cur = fresh_state(r, &bb.res[r.slot], calls + (size_t)bb.res[r.slot].call_row * np);
         cur.post = vp ? bb.post.data() + (size_t)bb.res[r.slot].call_row * np : nullptr;
+        cur.phase = vph ? bb.phase.data() + (size_t)bb.res[r.slot].call_row * np : nullptr;
         const int row = (cur.has_dq && !row_of.empty()) ? row_of[r.slot] : -1;
         if (row >= 0 && dnf_k > 0) cur.dnf = dnf.data() + (size_t)row * dnf_k;
         if (row >= 0 && dnc_k > 0) cur.dnc = dnc.data() + (size_t)row * dnc_k;
@@ -710,6 +746,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       st.qual = cur.qual; st.min = cur.min;
       if (cur.calls != st.calls.data()) std::copy(cur.calls, cur.calls + np, st.calls.begin());
       if (vp && cur.post != st.post.data()) std::copy(cur.post, cur.post + np, st.post.begin());
+      if (vph && cur.phase != st.phase.data()) std::copy(cur.phase, cur.phase + np, st.phase.begin());
     }
     {
       std::lock_guard<std::mutex> lk(free_mu);
@@ -997,7 +1034,8 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
 
   // exchange: {computed any, QUAL, AF minimiser, skipped records, Brent stuck, the genotype calls} of each rank's last
   // computed record
-  const int K = 5 + np + (vp ? 2 * np : 0);   // (--vcf_posteriors: each person's three floats in two more words)
+  // (--vcf_posteriors: each person's three floats in two more words; --vcf_phase: its two floats in one more, after those)
+  const int K = 5 + np + (vp ? 2 * np : 0) + (vph ? np : 0), kph = 5 + np + (vp ? 2 * np : 0);
   std::vector<int64_t> send(K), recv((size_t)N * K);
   send[0] = computed_any; send[1] = d2bits(st.qual); send[2] = d2bits(st.min); send[3] = bad_allele; send[4] = stuck;
   for (int p = 0; p < np; p++) send[5 + p] = pack_call(st.calls[p]);
@@ -1006,6 +1044,11 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     memcpy(b, st.post[p].p, sizeof(b));
     send[5 + np + 2 * p] = (int64_t)b[0] | ((int64_t)b[1] << 32);
     send[5 + np + 2 * p + 1] = (int64_t)b[2];
+  }
+  for (int p = 0; p < np && vph; p++) {
+    uint32_t b[2];
+    memcpy(b, &st.phase[p], sizeof(b));
+    send[kph + p] = (int64_t)b[0] | ((int64_t)b[1] << 32);
   }
   comm->allgather(send.data(), K, recv.data());
   int stuck_rank = -1;   // the first shard that met a stuck Brent: later shards' records come after it, never written
@@ -1017,6 +1060,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     State carried;
     carried.calls.assign(np, pm_vcf_call{0, 0, PM_LBL_VCF_DIPLOID, 0});
     if (vp) carried.post.assign(np, pm_vcf_post{{0.f, 0.f, 0.f}});
+    if (vph) carried.phase.assign(np, pm_vcf_phase{0.f, 0.f});
     for (int q = R - 1; q >= 0; q--) {
       const int64_t* v = recv.data() + (size_t)q * K;
       if (!v[0]) continue;
@@ -1027,6 +1071,10 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
         const uint32_t b[3] = {(uint32_t)(v[5 + np + 2 * p] & 0xFFFFFFFF), (uint32_t)((uint64_t)v[5 + np + 2 * p] >> 32),
                                (uint32_t)(v[5 + np + 2 * p + 1] & 0xFFFFFFFF)};
         memcpy(carried.post[p].p, b, sizeof(b));
+      }
+      for (int p = 0; p < np && vph; p++) {
+        const uint32_t b[2] = {(uint32_t)(v[kph + p] & 0xFFFFFFFF), (uint32_t)((uint64_t)v[kph + p] >> 32)};
+        memcpy(&carried.phase[p], b, sizeof(b));
       }
       break;
     }
