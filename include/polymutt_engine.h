@@ -524,6 +524,40 @@ int pm_engine_set_vcf_phase(pm_engine *eng, int32_t on);
  * batch returned.  PM_EINVAL: the feature is off, or a submitted batch has not been collected. */
 int pm_engine_vcf_phase(pm_engine *eng, int32_t *n_rows, pm_vcf_phase *out);
 
+/* The most probable joint genotype assignment of every family of every written record of a vcf_mode batch (additive to
+ * ABI 8: callers detect the feature by this symbol; the reference has no counterpart).  With (a1, a2) = (ref, alt) and
+ * the states 0, 1, 2 = a1a1, a1a2, a2a2, an assignment g of a family's members has the joint weight
+ *   J(g) = founder priors x the plain transmission T[g_fa][g_mo][g_c] of every non-founder x the members' penetrances
+ * at the site's frequency (pm_site_result.af) with the founder priors, the single-family prior mode and the family
+ * routing of the genotype rows, of pm_vcf_post and of pm_vcf_phase.  Every member of the family gets
+ *   g  = its state in an assignment g* with J(g*) = max J (ties: the first maximum of the kernel's fixed enumeration),
+ *   lp = log10(J(g*) / L),  L = the sum of J over all assignments: the same value for every member of the family,
+ * formed in double and rounded once to float.  A founders-only family factorises: each person's own best state, lp =
+ * the sum of the persons' log10 shares.  The rows' `best` is each person's marginal argmax, and marginal argmaxes need
+ * not be Mendelian-consistent; g* always is.  max J = 0 or L = 0: g = 255 and lp = 0 for the whole family, and so for
+ * every person of a chrX / chrY / MT section: sex-aware joint calls are not computed.  pad is written as 0. */
+typedef struct {
+  float lp;                    /* log10 posterior probability of the family's most probable joint assignment */
+  uint8_t g;                   /* this person's state in it: 0, 1, 2 = a1a1, a1a2, a2a2; 255 = none */
+  uint8_t pad[3];
+} pm_vcf_joint;
+
+/* Switch the joint call plane on or off (off at creation).  With it on, every batch runs one extra pass after the
+ * phase plane's (k_vcf_joint_lean / k_vcf_joint_nuc / k_vcf_joint_es, chosen as that pass's kernels are), which writes
+ * only the plane: the site results, the genotype rows, the posterior plane, the phase plane and the de novo outputs are
+ * those of the engine without it, byte for byte.  The device buffer is max_batch x n_person x 8 bytes, allocated on the
+ * first `on` and freed on `off` or pm_engine_destroy; off = nothing allocated, nothing launched.  Independent of
+ * pm_engine_set_vcf_posteriors, pm_engine_set_vcf_phase and the pm_engine_set_vcf_denovo family: any may be on without
+ * the others and none switches another off.  It may be set at any point between batches.  PM_EINVAL: an engine without
+ * vcf_mode, or a submitted batch not yet collected. */
+int pm_engine_set_vcf_joint(pm_engine *eng, int32_t on);
+
+/* The plane of the last finished batch (pm_engine_run, pm_engine_run_vcf or pm_engine_submit / pm_engine_collect):
+ * *n_rows = the batch's row count, out[row * n_person + person] with the rows of pm_site_result.call_row and the
+ * persons in pm_pedigree order.  out may be NULL (the count alone).  After PM_EBRENT: the same prefix of rows the
+ * batch returned.  PM_EINVAL: the feature is off, or a submitted batch has not been collected. */
+int pm_engine_vcf_joint(pm_engine *eng, int32_t *n_rows, pm_vcf_joint *out);
+
 /* Page-locked host memory for pm_engine_submit's inputs and the result rows (H2D/D2H at full PCIe rate). */
 int pm_host_alloc(uint64_t bytes, void **h_ptr);
 int pm_host_free(void *h_ptr);

@@ -8,6 +8,7 @@
 #include "vcf_denovo_dev.h"
 #include "vcf_post_dev.h"
 #include "vcf_phase_dev.h"
+#include "vcf_joint_dev.h"
 
 #define PM_BRENT_X(part, ...) extern template __global__ void k_brent<__VA_ARGS__>(DevArgs, int);
 PM_BRENT_VARIANTS
@@ -167,6 +168,13 @@ struct pm_engine {
   pm_vcf_phase* d_vph = nullptr;            // [max_batch][n_person]
   int* d_vph_kids[2] = {nullptr, nullptr};  // (family << 8 | member) of the non-founders of peeled families: plan 0 / plan 1
   std::vector<int> vph_kids_h[2];
+  // the joint call plane of vcf_mode batches (pm_engine_set_vcf_joint): off = no buffer, no launch
+  bool vj_on = false, vj_valid = false;     // vj_valid: the last finished batch filled the plane
+  pm_vcf_joint* d_vj = nullptr;             // [max_batch][n_person]
+  int* d_vj_fams[2] = {nullptr, nullptr};   // the peeled families: plan 0 / plan 1
+  std::vector<int> vj_fams_h[2];
+  double* d_vj_ws = nullptr;                // k_vcf_joint_es<false>'s workspace (only where the LDS one does not fit)
+  int vj_ws_per_lane = 0, vj_bt = 0, vj_grid = 0;   // doubles per thread; LDS block size (0: HBM); HBM grid
   std::vector<int> fam_kind_h, fam_perm_h;
   std::vector<int32_t> fa_h, mo_h;  // family-local parent indices (-1: none)
   unsigned long long* d_counters = nullptr;
@@ -390,7 +398,8 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf,
                   E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws, E->d_vdnx_terms, E->d_vdnx_ws, E->d_vw_row_site, E->d_vw_pfam, E->d_vw_fam_top, E->d_vw_fam_sum,
                   E->d_vw_fam_all, E->d_vw_fam_line, E->d_vw_car_top, E->d_vw_car_all, E->d_vw_car_line, E->d_vw_kids, E->d_vw_is_kid,
-                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf, E->d_vp, E->d_vph, E->d_vph_kids[0], E->d_vph_kids[1]};
+                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf, E->d_vp, E->d_vph, E->d_vph_kids[0], E->d_vph_kids[1],
+                  E->d_vj, E->d_vj_fams[0], E->d_vj_fams[1], E->d_vj_ws};
   for (void* b : bufs) if (b) hipFree(b);
   for (auto& pl : E->d_jit_slots)
     for (int* b : pl) if (b) hipFree(b);
@@ -621,6 +630,12 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
           const int p = ped->fam_start[e >> 8] + (e & 255), n = ped->fam_start[(e >> 8) + 1] - ped->fam_start[e >> 8];
           if (!ped->is_founder[p] && fa[p] >= 0 && mo[p] >= 0 && fa[p] < n && mo[p] < n && fa[p] != mo[p]) E->vph_kids_h[plan].push_back(e);
         }
+      // ... and the families themselves (k_vcf_joint_es; uploaded by pm_engine_set_vcf_joint)
+      for (int f = 0; f < ped->n_fam; f++) {
+        if (ped->fam_start[f + 1] - ped->fam_start[f] > 255) continue;
+        if (ped->fam_kind[f] == PM_FAM_EXTENDED) E->vj_fams_h[0].push_back(f);
+        if (ped->fam_kind[f] != PM_FAM_FOUNDERS) E->vj_fams_h[1].push_back(f);
+      }
       E->n_es_pers = (int)e0.size();
       E->n_es_pers1 = (int)e1.size();
       DALLOC(E->d_es_pers, std::max<size_t>(1, e0.size()));
@@ -1257,6 +1272,35 @@ static int launch_vcf_phase(pm_engine* E, const DevArgs& A, bool lean, bool es) 
   return PM_OK;
 }
 
+// The joint call plane of a vcf_mode batch's rows (vcf_joint_dev.h): one more pass behind the phase plane's, with
+// launch_vcf_phase's choice of kernels and launch shapes.  Sections that are not autosomal have no joint calls: their
+// plane is filled with (g = 255, lp = 0) instead.
+static int launch_vcf_joint(pm_engine* E, const DevArgs& A, bool lean, bool es) {
+  E->vj_valid = true;
+  if (E->chrom != PM_CHR_AUTO) {
+    hipLaunchKernelGGL(k_vcf_joint_none, dim3(E->grid_post), dim3(256), 0, E->stream, E->d_vj, (size_t)E->max_batch * E->n_person);
+    HIP_TRY(hipGetLastError());
+    return PM_OK;
+  }
+  const int plan = E->use_plan1 ? 1 : 0;
+  VjArgs P;
+  P.joint = E->d_vj; P.fams = E->d_vj_fams[plan]; P.n_fams = (int)E->vj_fams_h[plan].size();
+  P.ws = E->d_vj_ws; P.ws_per_lane = E->vj_ws_per_lane;
+  if (lean) hipLaunchKernelGGL(k_vcf_joint_lean, dim3(E->grid_post), dim3(256), (size_t)E->n_fam * 4, E->stream, A, P);
+  else hipLaunchKernelGGL(k_vcf_joint_nuc, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
+  HIP_TRY(hipGetLastError());
+  if (es && P.n_fams > 0) {   // launch_vcf_phase's choice between the LDS and the HBM workspace, at this pass's own size
+    const size_t per = (size_t)E->vj_ws_per_lane * sizeof(double);
+    if (E->vj_bt) {
+      const int per_cu = std::max(1, (int)((160 * 1024) / (per * E->vj_bt + 3 * 1024)));
+      hipLaunchKernelGGL(k_vcf_joint_es<true>, dim3(E->n_cu * per_cu * 2), dim3(E->vj_bt), per * E->vj_bt, E->stream, A, P);
+    } else
+      hipLaunchKernelGGL(k_vcf_joint_es<false>, dim3(E->vj_grid), dim3(256), 0, E->stream, A, P);
+    HIP_TRY(hipGetLastError());
+  }
+  return PM_OK;
+}
+
 static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* dm, const uint8_t* ref, pm_site_result* res,
                         pm_geno_call* calls) {
   DevArgs A = make_args(E, n, pl, dm, ref, res, calls);
@@ -1369,6 +1413,10 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
     if (E->vph_on) {
       HIP_TRY(hipGetLastError());
       if ((rc = launch_vcf_phase(E, A, lean, es))) return rc;
+    }
+    if (E->vj_on) {
+      HIP_TRY(hipGetLastError());
+      if ((rc = launch_vcf_joint(E, A, lean, es))) return rc;
     }
   }
   HIP_TRY(hipGetLastError());
@@ -1634,6 +1682,71 @@ int pm_engine_vcf_phase(pm_engine* E, int32_t* n_rows, pm_vcf_phase* out) {
     HIP_TRY(hipSetDevice(E->device));
     HIP_TRY(hipStreamSynchronize(E->stream));
     HIP_TRY(hipMemcpy(out, E->d_vph, sizeof(pm_vcf_phase) * (size_t)*n_rows * E->n_person, hipMemcpyDeviceToHost));
+  }
+  return PM_OK;
+}
+
+static void vj_free(pm_engine* E) {
+  E->vj_on = E->vj_valid = false;
+  void** bufs[] = {(void**)&E->d_vj, (void**)&E->d_vj_fams[0], (void**)&E->d_vj_fams[1], (void**)&E->d_vj_ws};
+  for (void** b : bufs) {
+    if (*b) (void)hipFree(*b);
+    *b = nullptr;
+  }
+}
+
+int pm_engine_set_vcf_joint(pm_engine* E, int32_t on) {
+  if (!E) { pm_set_last_error("pm_engine_set_vcf_joint: invalid arguments"); return PM_EINVAL; }
+  if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_joint: the engine was created without vcf_mode"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_vcf_joint: a submitted batch has not been collected"); return PM_EINVAL; }
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipStreamSynchronize(E->stream));
+  if (!on) { vj_free(E); return PM_OK; }
+  if (E->vj_on) return PM_OK;   // (already on: the last batch's plane stays)
+  // the max peel's workspace per thread: a back-pointer word per step on top of the partials [n][3] and the marriage
+  // partials [slots][9] that ws_per_lane covers (the sum peel for L runs in the same words)
+  int ws_need = E->ws_per_lane;
+  for (int f = 0; f < E->n_fam; f++) {
+    const int s0 = E->peel_start_h[f], s1 = E->peel_start_h[f + 1];
+    if (s1 == s0) continue;
+    int slots = 0;
+    for (int s = s0; s < s1; s++) {
+      const int slot = (E->steps_h[s].y >> 8) & 255;
+      if (slot != 255) slots = std::max(slots, slot + 1);
+    }
+    ws_need = std::max(ws_need, (E->fam_start_h[f + 1] - E->fam_start_h[f]) * 3 + slots * 9 + (s1 - s0));
+  }
+  E->vj_ws_per_lane = ws_need;
+  const size_t per = (size_t)ws_need * sizeof(double);
+  E->vj_bt = 0;
+  for (int t : {256, 128, 64})
+    if (!E->vj_bt && per * t <= 64 * 1024 && !E->sw.es_post_hbm) E->vj_bt = t;
+  E->vj_grid = per ? (int)std::max<size_t>(1, std::min<size_t>(E->grid_post, ((size_t)1 << 30) / (per * 256))) : E->grid_post;
+  const size_t cells = (size_t)E->max_batch * E->n_person;   // max_batch x n_person x 8 bytes
+  int rc = dalloc(&E->d_vj, cells);
+  const bool peels = !E->vj_fams_h[0].empty() || !E->vj_fams_h[1].empty();
+  if (!rc && peels && !E->vj_bt) rc = dalloc(&E->d_vj_ws, (size_t)E->vj_grid * 256 * ws_need);
+  for (int plan = 0; plan < 2 && !rc; plan++) {
+    const std::vector<int>& k = E->vj_fams_h[plan];
+    rc = dalloc(&E->d_vj_fams[plan], std::max<size_t>(1, k.size()));
+    if (!rc && !k.empty() && hipMemcpy(E->d_vj_fams[plan], k.data(), sizeof(int) * k.size(), hipMemcpyHostToDevice) != hipSuccess) rc = PM_EHIP;
+  }
+  if (!rc && hipMemset(E->d_vj, 0, cells * sizeof(pm_vcf_joint)) != hipSuccess) rc = PM_EHIP;
+  if (rc) { vj_free(E); return rc; }
+  E->vj_on = true;
+  E->vj_valid = false;   // (no batch has filled it yet)
+  return PM_OK;
+}
+
+int pm_engine_vcf_joint(pm_engine* E, int32_t* n_rows, pm_vcf_joint* out) {
+  if (!E || !n_rows) { pm_set_last_error("pm_engine_vcf_joint: invalid arguments"); return PM_EINVAL; }
+  if (!E->vj_on) { pm_set_last_error("pm_engine_vcf_joint: the feature is off (pm_engine_set_vcf_joint)"); return PM_EINVAL; }
+  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_vcf_joint: a submitted batch has not been collected"); return PM_EINVAL; }
+  *n_rows = E->vj_valid ? E->last_rows : 0;
+  if (out && *n_rows > 0) {
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipMemcpy(out, E->d_vj, sizeof(pm_vcf_joint) * (size_t)*n_rows * E->n_person, hipMemcpyDeviceToHost));
   }
   return PM_OK;
 }

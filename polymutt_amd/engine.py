@@ -107,6 +107,8 @@ VCF_POST_DTYPE = np.dtype([("p", "<f4", (3,))])   # pm_vcf_post
 assert VCF_POST_DTYPE.itemsize == 12
 VCF_PHASE_DTYPE = np.dtype([("p12", "<f4"), ("p21", "<f4")])   # pm_vcf_phase
 assert VCF_PHASE_DTYPE.itemsize == 8
+VCF_JOINT_DTYPE = np.dtype([("lp", "<f4"), ("g", "u1"), ("pad", "u1", (3,))])   # pm_vcf_joint
+assert VCF_JOINT_DTYPE.itemsize == 8
 
 _lib = None
 
@@ -141,6 +143,8 @@ EXPORTS = {
     "pm_engine_vcf_posteriors": (i32, [C.c_void_p, P(i32), C.c_void_p]),
     "pm_engine_set_vcf_phase": (i32, [C.c_void_p, i32]),
     "pm_engine_vcf_phase": (i32, [C.c_void_p, P(i32), C.c_void_p]),
+    "pm_engine_set_vcf_joint": (i32, [C.c_void_p, i32]),
+    "pm_engine_vcf_joint": (i32, [C.c_void_p, P(i32), C.c_void_p]),
     "pm_host_alloc": (i32, [u64, P(C.c_void_p)]),
     "pm_host_free": (i32, [C.c_void_p]),
     "pm_engine_to_planar": (i32, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
@@ -526,6 +530,25 @@ class Engine:
         ph = np.zeros((n.value, self.n_person), dtype=VCF_PHASE_DTYPE)
         self._check(self.lib.pm_engine_vcf_phase(self.h, C.byref(n), _ptr(ph)))
         return np.stack([ph["p12"], ph["p21"]], axis=-1)
+
+    def set_vcf_joint(self, on=True):
+        """pm_engine_set_vcf_joint (vcf_mode engines): every batch also keeps, for every family of every written row of
+        an autosomal section, its most probable joint genotype assignment; off (the default) allocates and launches
+        nothing.  Every other output is the same bytes either way."""
+        self._check(self.lib.pm_engine_set_vcf_joint(self.h, 1 if on else 0))
+
+    def vcf_joint(self):
+        """pm_engine_vcf_joint for the last finished batch: (g uint8 [rows, n_person], lp float32 [rows, n_person]) --
+        each person's state (0, 1, 2; 255: none) in its family's most probable joint assignment and the log10 posterior
+        of that assignment, the same for every member of a family; rows indexed by call_row (after a stuck Brent: the
+        rows the batch returned)."""
+        n = i32(0)
+        self._check(self.lib.pm_engine_vcf_joint(self.h, C.byref(n), None))
+        if not n.value:
+            return np.zeros((0, self.n_person), dtype=np.uint8), np.zeros((0, self.n_person), dtype=np.float32)
+        jt = np.zeros((n.value, self.n_person), dtype=VCF_JOINT_DTYPE)
+        self._check(self.lib.pm_engine_vcf_joint(self.h, C.byref(n), _ptr(jt)))
+        return jt["g"].copy(), jt["lp"].copy()
 
     def stuck_site(self):
         """pm_engine_stuck_site: the first site of the last finished batch whose Brent hit ITMAX (-1: none)."""

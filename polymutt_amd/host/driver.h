@@ -57,6 +57,10 @@ struct Options {
   bool vcf_phase = false;
   int vcf_phase_minPQ = 10;
   bool vcf_phase_minPQ_given = false;
+  // --vcf_joint (with --in_vcf): every sample of every written record also gets JG and JL before PL / GL, its genotype in
+  // its family's most probable joint (Mendelian-consistent) assignment and the log10 posterior of that assignment
+  // (pm_engine_set_vcf_joint); GT stays the marginal call; combines freely with the other --vcf_ flags
+  bool vcf_joint = false;
   std::string cmd;
   pm_params params() const;
 };
@@ -137,6 +141,9 @@ class SiteEvaluator {
   // --vcf_phase: the same pair for the transmission phase plane (pm_engine_set_vcf_phase / pm_engine_vcf_phase)
   virtual void set_vcf_phase(bool on) { (void)on; throw FatalError("--vcf_phase is not supported by this evaluator\n"); }
   virtual int vcf_phase(pm_vcf_phase* out) { (void)out; throw FatalError("--vcf_phase is not supported by this evaluator\n"); }
+  // --vcf_joint: the same pair for the joint call plane (pm_engine_set_vcf_joint / pm_engine_vcf_joint)
+  virtual void set_vcf_joint(bool on) { (void)on; throw FatalError("--vcf_joint is not supported by this evaluator\n"); }
+  virtual int vcf_joint(pm_vcf_joint* out) { (void)out; throw FatalError("--vcf_joint is not supported by this evaluator\n"); }
   // Host memory for the batch buffers (the engine: page-locked, for asynchronous copies)
   virtual void* host_alloc(size_t bytes);
   virtual void host_free(void* p);

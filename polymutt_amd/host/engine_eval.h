@@ -160,6 +160,15 @@ class EngineEvaluator : public SiteEvaluator {
     check(pm_engine_vcf_phase(last_, &n, out));
     return n;
   }
+  void set_vcf_joint(bool on) override {
+    for (auto* e : eng_) check(pm_engine_set_vcf_joint(e, on ? 1 : 0));
+  }
+  int vcf_joint(pm_vcf_joint* out) override {   // (the engine that ran the batch last returned)
+    if (!last_) throw FatalError("GPU engine error: no finished batch\n");
+    int32_t n = 0;
+    check(pm_engine_vcf_joint(last_, &n, out));
+    return n;
+  }
   void* host_alloc(size_t bytes) override {
     void* p = nullptr;
     if (pm_host_alloc(bytes ? bytes : 1, &p) != PM_OK || !p) return SiteEvaluator::host_alloc(bytes);   // pageable fallback

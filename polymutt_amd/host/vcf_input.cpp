@@ -253,6 +253,7 @@ struct State {            // what FamilyLikelihoodSeq_VCF holds between records 
   std::vector<pm_vcf_call> calls;    // per flattened person
   std::vector<pm_vcf_post> post;     // --vcf_posteriors: their posteriors (all zero before the first computed record)
   std::vector<pm_vcf_phase> phase;   // --vcf_phase: their transmission phase (likewise)
+  std::vector<pm_vcf_joint> joint;   // --vcf_joint: their joint calls (g = 255 before the first computed record)
   int a_ref = 0;                     // allele of the label convention (always allele1 in this path)
 };
 
@@ -367,6 +368,10 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     if (opt.vcf_phase)   // (--vcf_phase: no reference counterpart)
       fprintf(out, "%s",
               "##FORMAT=<ID=PQ,Number=1,Type=Integer,Description=\"Phred-scaled quality of the transmission phase of GT (paternal|maternal)\">\n");
+    if (opt.vcf_joint)   // (--vcf_joint: no reference counterpart)
+      fprintf(out, "%s",
+              "##FORMAT=<ID=JG,Number=1,Type=String,Description=\"Genotype in the Family's Most Probable Joint Configuration\">\n"
+              "##FORMAT=<ID=JL,Number=1,Type=Float,Description=\"Log10 Posterior Probability of That Configuration\">\n");
     fprintf(out, "%s",
             "##FORMAT=<ID=PL,Number=3,Type=Integer,Description=\"Phred-scaled Genotype Likelihoods\">\n"
             "##FORMAT=<ID=GL,Number=3,Type=Float,Description=\"Log10 Genotype Likelihoods\">\n");
@@ -395,6 +400,9 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   const bool vph = opt.vcf_phase;
   const int min_pq = opt.vcf_phase_minPQ;
   if (vph) eval.set_vcf_phase(true);
+  const bool vj = opt.vcf_joint;
+  if (vj) eval.set_vcf_joint(true);
+  const pm_vcf_joint no_joint = {0.f, 255, {0, 0, 0}};
   const int B = std::max(1, opt.batch);
   // Two batches: the main thread reads, classifies and parses records into one while the flusher thread runs the
   // engine on the other, formats its records and hands their text to the writer thread.  A batch's PL rows are in
@@ -411,13 +419,15 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     std::vector<Pending*> pend;
     std::vector<pm_vcf_post> post;   // --vcf_posteriors: the batch's posterior plane, fetched next to the calls
     std::vector<pm_vcf_phase> phase; // --vcf_phase: the batch's phase plane, likewise
+    std::vector<pm_vcf_joint> joint; // --vcf_joint: the batch's joint call plane, likewise
     int nb = 0;
-    BatchBuf(SiteEvaluator& ev, int b, int n, bool with_post, bool with_phase)
+    BatchBuf(SiteEvaluator& ev, int b, int n, bool with_post, bool with_phase, bool with_joint)
         : e(ev), pl((uint8_t*)ev.host_alloc((size_t)b * n * 10)), calls((pm_vcf_call*)ev.host_alloc((size_t)b * n * sizeof(pm_vcf_call))),
-          ref(b), res(b), post(with_post ? (size_t)b * n : 0), phase(with_phase ? (size_t)b * n : 0) {}
+          ref(b), res(b), post(with_post ? (size_t)b * n : 0), phase(with_phase ? (size_t)b * n : 0),
+          joint(with_joint ? (size_t)b * n : 0) {}
     ~BatchBuf() { e.host_free(pl); e.host_free(calls); }
   };
-  BatchBuf bb0(eval, B, np, vp, vph), bb1(eval, B, np, vp, vph);
+  BatchBuf bb0(eval, B, np, vp, vph, vj), bb1(eval, B, np, vp, vph, vj);
   BatchBuf* const bbs[2] = {&bb0, &bb1};
   if (!bb0.pl || !bb1.pl || !bb0.calls || !bb1.calls) throw FatalError("out of host memory\n");
   int cb = 0;   // the batch the main thread fills
@@ -443,6 +453,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   st.calls.assign(np, pm_vcf_call{0, 0, PM_LBL_VCF_DIPLOID, 0});
   if (vp) st.post.assign(np, pm_vcf_post{{0.f, 0.f, 0.f}});
   if (vph) st.phase.assign(np, pm_vcf_phase{0.f, 0.f});
+  if (vj) st.joint.assign(np, no_joint);
 
   // The state a record is printed with: its own (a computed record) or the previous computed record's (a record
   // without data, PedVCF.cpp:113-122): QUAL, the AF minimiser and every person's call.
@@ -457,6 +468,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     const pm_person_dn* dnc = nullptr;
     const pm_vcf_post* post = nullptr;   // --vcf_posteriors: every person's posteriors, carried like the calls
     const pm_vcf_phase* phase = nullptr; // --vcf_phase: every person's transmission phase, carried like the calls
+    const pm_vcf_joint* joint = nullptr; // --vcf_joint: every person's joint call, carried like the calls
   };
   auto fresh_state = [&](const Pending& r, const pm_site_result* Rs, const pm_vcf_call* C) {
     // mono/poly -> QUAL (PedVCF.cpp:136-152), with the reference's operator-precedence slip
@@ -517,8 +529,9 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       fv[s] = F;
       if (F.db >= 0) totalDepth += atoi_fast(lp + F.db);
     }
-    // (--vcf_posteriors: at most 32 more characters per sample; --vcf_phase: at most 3, PQ and its colon)
-    out.resize(L.size() + ((vp ? 49 : 17) + (vph ? 3 : 0)) * ns + 1024);
+    // (--vcf_posteriors: at most 32 more characters per sample; --vcf_phase: at most 3, PQ and its colon; --vcf_joint: at
+    // most 32, JG, JL -- a float's log10 has at most 3 digits before the point -- and their colons)
+    out.resize(L.size() + ((vp ? 49 : 17) + (vph ? 3 : 0) + (vj ? 32 : 0)) * ns + 1024);
     char* w = &out[0];
     auto put = [&](const char* p, size_t n) { memcpy(w, p, n); w += n; };
     auto fld = [&](int k) { put(lp + r.cols[k].b, (size_t)(r.cols[k].e - r.cols[k].b)); };
@@ -539,6 +552,12 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     const bool has_pl = fs.PL_idx > 0;
     const char* fmt_s = vp ? (vph ? (has_pl ? "GT:GQ:DP:DS:GP:PQ:PL" : "GT:GQ:DP:DS:GP:PQ:GL") : has_pl ? "GT:GQ:DP:DS:GP:PL" : "GT:GQ:DP:DS:GP:GL")
                            : (vph ? (has_pl ? "GT:GQ:DP:PQ:PL" : "GT:GQ:DP:PQ:GL") : has_pl ? "GT:GQ:DP:PL" : "GT:GQ:DP:GL");
+    std::string fmt_j;
+    if (vj) {   // JG:JL directly before PL / GL
+      fmt_j.assign(fmt_s, strlen(fmt_s) - 2);
+      fmt_j += has_pl ? "JG:JL:PL" : "JG:JL:GL";
+      fmt_s = fmt_j.c_str();
+    }
     std::string dq_t;
     if (S.has_dq) {
       char v[64];
@@ -622,6 +641,16 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
         else *w++ = '.';
         *w++ = ':';
       }
+      if (vj) {   // JG:JL of the person's family (a ./. sample still gets its values; "." without an assignment)
+        const pm_vcf_joint& q = S.joint[inc_cols[s].second];
+        if (q.g > 2) put(".:.", 3);
+        else {
+          put(kDip[q.g], 3);
+          *w++ = ':';
+          w += snprintf(w, 24, "%.2f", (double)q.lp);
+        }
+        *w++ = ':';
+      }
       if (F.pb >= 0) put(lp + F.pb, (size_t)(F.pe - F.pb));
       else *w++ = '.';
     }
@@ -633,6 +662,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     RecState S{st.qual, st.min, st.calls.data()};
     S.post = st.post.data();
     S.phase = st.phase.data();
+    S.joint = st.joint.data();
     std::string t;
     format_record(t, r, S);
     fwrite(t.data(), 1, t.size(), fo);
@@ -692,6 +722,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       }
       if (vp) eval.vcf_posteriors(bb.post.data());   // (after a stuck Brent: the rows of the records that still go out)
       if (vph) eval.vcf_phase(bb.phase.data());
+      if (vj) eval.vcf_joint(bb.joint.data());
     }
     // the batch's rows (the sites with DQ at or above the threshold; after a stuck Brent those before it): slot -> row
     std::vector<int32_t> row_of;
@@ -714,12 +745,14 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     RecState cur{st.qual, st.min, st.calls.data()};
     cur.post = st.post.data();
     cur.phase = st.phase.data();
+    cur.joint = st.joint.data();
     for (size_t k = 0; k < npend; k++) {
       const Pending& r = *pend[k];
       if (r.computed) {
         cur = fresh_state(r, &bb.res[r.slot], calls + (size_t)bb.res[r.slot].call_row * np);
         cur.post = vp ? bb.post.data() + (size_t)bb.res[r.slot].call_row * np : nullptr;
         cur.phase = vph ? bb.phase.data() + (size_t)bb.res[r.slot].call_row * np : nullptr;
+        cur.joint = vj ? bb.joint.data() + (size_t)bb.res[r.slot].call_row * np : nullptr;
         const int row = (cur.has_dq && !row_of.empty()) ? row_of[r.slot] : -1;
         if (row >= 0 && dnf_k > 0) cur.dnf = dnf.data() + (size_t)row * dnf_k;
         if (row >= 0 && dnc_k > 0) cur.dnc = dnc.data() + (size_t)row * dnc_k;
@@ -747,6 +780,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       if (cur.calls != st.calls.data()) std::copy(cur.calls, cur.calls + np, st.calls.begin());
       if (vp && cur.post != st.post.data()) std::copy(cur.post, cur.post + np, st.post.begin());
       if (vph && cur.phase != st.phase.data()) std::copy(cur.phase, cur.phase + np, st.phase.begin());
+      if (vj && cur.joint != st.joint.data()) std::copy(cur.joint, cur.joint + np, st.joint.begin());
     }
     {
       std::lock_guard<std::mutex> lk(free_mu);
@@ -1034,8 +1068,9 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
 
   // exchange: {computed any, QUAL, AF minimiser, skipped records, Brent stuck, the genotype calls} of each rank's last
   // computed record
-  // (--vcf_posteriors: each person's three floats in two more words; --vcf_phase: its two floats in one more, after those)
-  const int K = 5 + np + (vp ? 2 * np : 0) + (vph ? np : 0), kph = 5 + np + (vp ? 2 * np : 0);
+  // (--vcf_posteriors: each person's three floats in two more words; --vcf_phase: its two floats in one more, after those;
+  // --vcf_joint: its 8 bytes in one more, after those)
+  const int kph = 5 + np + (vp ? 2 * np : 0), kj = kph + (vph ? np : 0), K = kj + (vj ? np : 0);
   std::vector<int64_t> send(K), recv((size_t)N * K);
   send[0] = computed_any; send[1] = d2bits(st.qual); send[2] = d2bits(st.min); send[3] = bad_allele; send[4] = stuck;
   for (int p = 0; p < np; p++) send[5 + p] = pack_call(st.calls[p]);
@@ -1050,6 +1085,11 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     memcpy(b, &st.phase[p], sizeof(b));
     send[kph + p] = (int64_t)b[0] | ((int64_t)b[1] << 32);
   }
+  for (int p = 0; p < np && vj; p++) {
+    uint32_t b[2];
+    memcpy(b, &st.joint[p], sizeof(b));
+    send[kj + p] = (int64_t)b[0] | ((int64_t)b[1] << 32);
+  }
   comm->allgather(send.data(), K, recv.data());
   int stuck_rank = -1;   // the first shard that met a stuck Brent: later shards' records come after it, never written
   for (int q = N - 1; q >= 0; q--)
@@ -1061,6 +1101,7 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     carried.calls.assign(np, pm_vcf_call{0, 0, PM_LBL_VCF_DIPLOID, 0});
     if (vp) carried.post.assign(np, pm_vcf_post{{0.f, 0.f, 0.f}});
     if (vph) carried.phase.assign(np, pm_vcf_phase{0.f, 0.f});
+    if (vj) carried.joint.assign(np, no_joint);
     for (int q = R - 1; q >= 0; q--) {
       const int64_t* v = recv.data() + (size_t)q * K;
       if (!v[0]) continue;
@@ -1075,6 +1116,10 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
       for (int p = 0; p < np && vph; p++) {
         const uint32_t b[2] = {(uint32_t)(v[kph + p] & 0xFFFFFFFF), (uint32_t)((uint64_t)v[kph + p] >> 32)};
         memcpy(&carried.phase[p], b, sizeof(b));
+      }
+      for (int p = 0; p < np && vj; p++) {
+        const uint32_t b[2] = {(uint32_t)(v[kj + p] & 0xFFFFFFFF), (uint32_t)((uint64_t)v[kj + p] >> 32)};
+        memcpy(&carried.joint[p], b, sizeof(b));
       }
       break;
     }
