@@ -6,6 +6,7 @@
 #include "brent_plan.h"
 #include "brent_variants.h"
 #include "vcf_denovo_dev.h"
+#include "vcf_plane_dev.h"
 #include "vcf_post_dev.h"
 #include "vcf_phase_dev.h"
 #include "vcf_joint_dev.h"
@@ -29,6 +30,20 @@ extern "C" const char* pm_last_error(void) { return g_last_error.c_str(); }
 extern "C" int pm_abi_version(void) { return PM_ABI_VERSION; }
 // ================================================================================================
 // host side
+// One output plane of vcf_mode batches, [max_batch][n_person] cells: off = no buffer, no launch
+struct Plane {
+  size_t cell;                      // bytes per (row, person)
+  void* d = nullptr;
+  bool on = false, valid = false;   // valid: the last finished batch filled the plane
+};
+// An index list per lane plan (0 / 1) that a plane's peel kernel walks: built with the engine, on the device while the plane is on
+struct PlanList {
+  std::vector<int> h[2];
+  int* d[2] = {nullptr, nullptr};
+  int upload();
+  void free();
+};
+
 struct pm_engine {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -160,21 +175,13 @@ struct pm_engine {
   int2* d_vwx_kids = nullptr;                                           // every person with both parents in the family
   int8_t* d_vwx_is_kid = nullptr;
   double* d_vwx_jbuf = nullptr;                                         // [vwx_grid][vwx_n_kids * 13]
-  // the genotype posterior plane of vcf_mode batches (pm_engine_set_vcf_posteriors): off = no buffer, no launch
-  bool vp_on = false, vp_valid = false;   // vp_valid: the last finished batch filled the plane
-  pm_vcf_post* d_vp = nullptr;            // [max_batch][n_person]
-  // the transmission phase plane of vcf_mode batches (pm_engine_set_vcf_phase): off = no buffer, no launch
-  bool vph_on = false, vph_valid = false;   // vph_valid: the last finished batch filled the plane
-  pm_vcf_phase* d_vph = nullptr;            // [max_batch][n_person]
-  int* d_vph_kids[2] = {nullptr, nullptr};  // (family << 8 | member) of the non-founders of peeled families: plan 0 / plan 1
-  std::vector<int> vph_kids_h[2];
-  // the joint call plane of vcf_mode batches (pm_engine_set_vcf_joint): off = no buffer, no launch
-  bool vj_on = false, vj_valid = false;     // vj_valid: the last finished batch filled the plane
-  pm_vcf_joint* d_vj = nullptr;             // [max_batch][n_person]
-  int* d_vj_fams[2] = {nullptr, nullptr};   // the peeled families: plan 0 / plan 1
-  std::vector<int> vj_fams_h[2];
+  // the output planes of vcf_mode batches: genotype posteriors (pm_engine_set_vcf_posteriors), transmission phase
+  // (pm_engine_set_vcf_phase), joint calls (pm_engine_set_vcf_joint)
+  Plane vp{sizeof(pm_vcf_post)}, vph{sizeof(pm_vcf_phase)}, vj{sizeof(pm_vcf_joint)};
+  PlanList vph_kids;                        // (family << 8 | member) of the non-founders of peeled families
+  PlanList vj_fams;                         // the peeled families
   double* d_vj_ws = nullptr;                // k_vcf_joint_es<false>'s workspace (only where the LDS one does not fit)
-  int vj_ws_per_lane = 0, vj_bt = 0, vj_grid = 0;   // doubles per thread; LDS block size (0: HBM); HBM grid
+  int vj_ws_per_lane = 0, vj_grid = 0;      // doubles per thread; HBM grid
   std::vector<int> fam_kind_h, fam_perm_h;
   std::vector<int32_t> fa_h, mo_h;  // family-local parent indices (-1: none)
   unsigned long long* d_counters = nullptr;
@@ -218,6 +225,20 @@ static int dalloc(X** p, size_t count) {
     return PM_ENOMEM;
   }
   return PM_OK;
+}
+static void dfree(void** p) {
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+}
+int PlanList::upload() {
+  for (int plan = 0; plan < 2; plan++) {
+    if (int rc = dalloc(&d[plan], std::max<size_t>(1, h[plan].size()))) return rc;
+    if (!h[plan].empty()) HIP_TRY(hipMemcpy(d[plan], h[plan].data(), sizeof(int) * h[plan].size(), hipMemcpyHostToDevice));
+  }
+  return PM_OK;
+}
+void PlanList::free() {
+  for (int plan = 0; plan < 2; plan++) dfree((void**)&d[plan]);
 }
 // a persistent grid rounded down to whole rounds of the 8 XCDs (the kernels' XCD-aware item order needs gridDim % 8 == 0;
 // they fall back to plain order otherwise), never below one block
@@ -398,9 +419,10 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf,
                   E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws, E->d_vdnx_terms, E->d_vdnx_ws, E->d_vw_row_site, E->d_vw_pfam, E->d_vw_fam_top, E->d_vw_fam_sum,
                   E->d_vw_fam_all, E->d_vw_fam_line, E->d_vw_car_top, E->d_vw_car_all, E->d_vw_car_line, E->d_vw_kids, E->d_vw_is_kid,
-                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf, E->d_vp, E->d_vph, E->d_vph_kids[0], E->d_vph_kids[1],
-                  E->d_vj, E->d_vj_fams[0], E->d_vj_fams[1], E->d_vj_ws};
+                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf, E->vp.d, E->vph.d, E->vj.d, E->d_vj_ws};
   for (void* b : bufs) if (b) hipFree(b);
+  E->vph_kids.free();
+  E->vj_fams.free();
   for (auto& pl : E->d_jit_slots)
     for (int* b : pl) if (b) hipFree(b);
   for (auto& pl : E->d_fused_tab)
@@ -628,13 +650,13 @@ int pm_engine_create(const pm_pedigree* ped, const pm_params* par, int device, i
       for (int plan = 0; plan < 2; plan++)
         for (int e : plan ? e1 : e0) {
           const int p = ped->fam_start[e >> 8] + (e & 255), n = ped->fam_start[(e >> 8) + 1] - ped->fam_start[e >> 8];
-          if (!ped->is_founder[p] && fa[p] >= 0 && mo[p] >= 0 && fa[p] < n && mo[p] < n && fa[p] != mo[p]) E->vph_kids_h[plan].push_back(e);
+          if (!ped->is_founder[p] && fa[p] >= 0 && mo[p] >= 0 && fa[p] < n && mo[p] < n && fa[p] != mo[p]) E->vph_kids.h[plan].push_back(e);
         }
       // ... and the families themselves (k_vcf_joint_es; uploaded by pm_engine_set_vcf_joint)
       for (int f = 0; f < ped->n_fam; f++) {
         if (ped->fam_start[f + 1] - ped->fam_start[f] > 255) continue;
-        if (ped->fam_kind[f] == PM_FAM_EXTENDED) E->vj_fams_h[0].push_back(f);
-        if (ped->fam_kind[f] != PM_FAM_FOUNDERS) E->vj_fams_h[1].push_back(f);
+        if (ped->fam_kind[f] == PM_FAM_EXTENDED) E->vj_fams.h[0].push_back(f);
+        if (ped->fam_kind[f] != PM_FAM_FOUNDERS) E->vj_fams.h[1].push_back(f);
       }
       E->n_es_pers = (int)e0.size();
       E->n_es_pers1 = (int)e1.size();
@@ -1218,87 +1240,80 @@ static int launch_vcf_denovo_x(pm_engine* E, const DevArgs& A) {
   return launch_vdn_who(E, A, E->vdnx_T == 64 ? k_vdn_who_x<64> : k_vdn_who_x<256>, E->vwx_grid, E->vdnx_T, V, W);
 }
 
-// The posterior plane of a vcf_mode batch's rows (vcf_post_dev.h): one more pass behind the standard posterior stage, with
-// that stage's choice of kernels (lean: k_posterior_lean ran; es: the section has peeled families) and launch shapes.
-static int launch_vcf_posteriors(pm_engine* E, const DevArgs& A, bool lean, bool es) {
-  VpArgs P;
-  P.post = E->d_vp;
-  if (lean) hipLaunchKernelGGL(k_vcf_post_lean, dim3(E->grid_post), dim3(256), (size_t)E->n_fam * 4, E->stream, A, P);
-  else hipLaunchKernelGGL(k_vcf_post_nuc, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
+// The launch shape of a peel kernel that needs ws_per_lane doubles of workspace per thread.  The workspace goes to dynamic
+// LDS when a block's share fits the 64 KB default dynamic-LDS limit: bt is the largest of 256 / 128 / 64 threads that does,
+// the grid twice the blocks that 160 KB of LDS per CU hold (3 KB of static LDS and padding per block).  bt = 0 (nothing
+// fits, or PM_ES_POST_HBM): the kernel's HBM-workspace form at grid_post x 256.
+struct EsShape { int bt, grid; size_t lds_bytes; };
+static EsShape es_block_shape(const pm_engine* E, int ws_per_lane) {
+  const size_t per = (size_t)ws_per_lane * sizeof(double);
+  for (int t : {256, 128, 64})
+    if (per * t <= 64 * 1024 && !E->sw.es_post_hbm) {
+      const int per_cu = std::max(1, (int)((160 * 1024) / (per * t + 3 * 1024)));
+      return {t, E->n_cu * per_cu * 2, per * t};
+    }
+  return {0, E->grid_post, 0};
+}
+
+// One plane's pass over a vcf_mode batch's rows, behind the standard posterior stage and with that stage's routing: the
+// lean kernel (lean_lds bytes of family table) where k_posterior_lean ran, else the nuc kernel, both at the stage's grid;
+// then, where the section has peeled families (es) and the plane's list n_items entries, the plane's peel kernel at shape
+// sh, its HBM form at hbm_grid blocks.  (A template over the plane's args: C++ linkage inside this file's extern "C".)
+extern "C++" template <class PA>
+static int launch_plane_pass(pm_engine* E, const DevArgs& A, const PA& P, bool lean, void (*k_lean)(DevArgs, PA), size_t lean_lds,
+                             void (*k_nuc)(DevArgs, PA), bool es, int n_items, void (*k_es_lds)(DevArgs, PA),
+                             void (*k_es_hbm)(DevArgs, PA), const EsShape& sh, int hbm_grid) {
+  if (lean) hipLaunchKernelGGL(k_lean, dim3(E->grid_post), dim3(256), lean_lds, E->stream, A, P);
+  else hipLaunchKernelGGL(k_nuc, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
   HIP_TRY(hipGetLastError());
-  if (es && A.n_es_pers > 0) {   // k_posterior_es's choice between the LDS and the HBM workspace
-    const size_t per = (size_t)E->ws_per_lane * sizeof(double);
-    int bt = 0;
-    for (int t : {256, 128, 64})
-      if (!bt && per * t <= 64 * 1024 && !E->sw.es_post_hbm) bt = t;
-    if (bt) {
-      const int per_cu = std::max(1, (int)((160 * 1024) / (per * bt + 3 * 1024)));
-      hipLaunchKernelGGL(k_vcf_post_es<true>, dim3(E->n_cu * per_cu * 2), dim3(bt), per * bt, E->stream, A, P);
-    } else
-      hipLaunchKernelGGL(k_vcf_post_es<false>, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
+  if (es && n_items > 0) {
+    if (sh.bt) hipLaunchKernelGGL(k_es_lds, dim3(sh.grid), dim3(sh.bt), sh.lds_bytes, E->stream, A, P);
+    else hipLaunchKernelGGL(k_es_hbm, dim3(hbm_grid), dim3(256), 0, E->stream, A, P);
     HIP_TRY(hipGetLastError());
   }
-  E->vp_valid = true;
   return PM_OK;
 }
 
-// The transmission phase plane of a vcf_mode batch's rows (vcf_phase_dev.h): one more pass behind the standard posterior
-// stage and the posterior plane's, with launch_vcf_posteriors' choice of kernels and launch shapes.  Sections that are not
-// autosomal have no phase: their plane is cleared instead.
+// The posterior plane (vcf_post_dev.h), on every chromosome class.
+static int launch_vcf_posteriors(pm_engine* E, const DevArgs& A, bool lean, bool es) {
+  VpArgs P;
+  P.post = (pm_vcf_post*)E->vp.d;
+  if (int rc = launch_plane_pass(E, A, P, lean, k_vcf_post_lean, (size_t)E->n_fam * 4, k_vcf_post_nuc, es, A.n_es_pers, k_vcf_post_es<true>,
+                                 k_vcf_post_es<false>, es_block_shape(E, E->ws_per_lane), E->grid_post))
+    return rc;
+  E->vp.valid = true;
+  return PM_OK;
+}
+
+// The transmission phase plane (vcf_phase_dev.h).  Sections that are not autosomal have no phase: their plane is cleared.
 static int launch_vcf_phase(pm_engine* E, const DevArgs& A, bool lean, bool es) {
-  E->vph_valid = true;
+  E->vph.valid = true;
   if (E->chrom != PM_CHR_AUTO) {
-    HIP_TRY(hipMemsetAsync(E->d_vph, 0, sizeof(pm_vcf_phase) * (size_t)E->max_batch * E->n_person, E->stream));
+    HIP_TRY(hipMemsetAsync(E->vph.d, 0, sizeof(pm_vcf_phase) * (size_t)E->max_batch * E->n_person, E->stream));
     return PM_OK;
   }
   const int plan = E->use_plan1 ? 1 : 0;
   VphArgs P;
-  P.phase = E->d_vph; P.kids = E->d_vph_kids[plan]; P.n_kids = (int)E->vph_kids_h[plan].size();
-  if (lean) hipLaunchKernelGGL(k_vcf_phase_lean, dim3(E->grid_post), dim3(256), (size_t)E->n_fam * 5, E->stream, A, P);
-  else hipLaunchKernelGGL(k_vcf_phase_nuc, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
-  HIP_TRY(hipGetLastError());
-  if (es && P.n_kids > 0) {   // k_posterior_es's choice between the LDS and the HBM workspace
-    const size_t per = (size_t)E->ws_per_lane * sizeof(double);
-    int bt = 0;
-    for (int t : {256, 128, 64})
-      if (!bt && per * t <= 64 * 1024 && !E->sw.es_post_hbm) bt = t;
-    if (bt) {
-      const int per_cu = std::max(1, (int)((160 * 1024) / (per * bt + 3 * 1024)));
-      hipLaunchKernelGGL(k_vcf_phase_es<true>, dim3(E->n_cu * per_cu * 2), dim3(bt), per * bt, E->stream, A, P);
-    } else
-      hipLaunchKernelGGL(k_vcf_phase_es<false>, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
-    HIP_TRY(hipGetLastError());
-  }
-  return PM_OK;
+  P.phase = (pm_vcf_phase*)E->vph.d; P.kids = E->vph_kids.d[plan]; P.n_kids = (int)E->vph_kids.h[plan].size();
+  return launch_plane_pass(E, A, P, lean, k_vcf_phase_lean, (size_t)E->n_fam * 5, k_vcf_phase_nuc, es, P.n_kids, k_vcf_phase_es<true>,
+                           k_vcf_phase_es<false>, es_block_shape(E, E->ws_per_lane), E->grid_post);
 }
 
-// The joint call plane of a vcf_mode batch's rows (vcf_joint_dev.h): one more pass behind the phase plane's, with
-// launch_vcf_phase's choice of kernels and launch shapes.  Sections that are not autosomal have no joint calls: their
-// plane is filled with (g = 255, lp = 0) instead.
+// The joint call plane (vcf_joint_dev.h), its peel at this pass's own workspace size and HBM grid.  Sections that are not
+// autosomal have no joint calls: their plane is filled with (g = 255, lp = 0).
 static int launch_vcf_joint(pm_engine* E, const DevArgs& A, bool lean, bool es) {
-  E->vj_valid = true;
+  E->vj.valid = true;
   if (E->chrom != PM_CHR_AUTO) {
-    hipLaunchKernelGGL(k_vcf_joint_none, dim3(E->grid_post), dim3(256), 0, E->stream, E->d_vj, (size_t)E->max_batch * E->n_person);
+    hipLaunchKernelGGL(k_vcf_joint_none, dim3(E->grid_post), dim3(256), 0, E->stream, (pm_vcf_joint*)E->vj.d, (size_t)E->max_batch * E->n_person);
     HIP_TRY(hipGetLastError());
     return PM_OK;
   }
   const int plan = E->use_plan1 ? 1 : 0;
   VjArgs P;
-  P.joint = E->d_vj; P.fams = E->d_vj_fams[plan]; P.n_fams = (int)E->vj_fams_h[plan].size();
+  P.joint = (pm_vcf_joint*)E->vj.d; P.fams = E->vj_fams.d[plan]; P.n_fams = (int)E->vj_fams.h[plan].size();
   P.ws = E->d_vj_ws; P.ws_per_lane = E->vj_ws_per_lane;
-  if (lean) hipLaunchKernelGGL(k_vcf_joint_lean, dim3(E->grid_post), dim3(256), (size_t)E->n_fam * 4, E->stream, A, P);
-  else hipLaunchKernelGGL(k_vcf_joint_nuc, dim3(E->grid_post), dim3(256), 0, E->stream, A, P);
-  HIP_TRY(hipGetLastError());
-  if (es && P.n_fams > 0) {   // launch_vcf_phase's choice between the LDS and the HBM workspace, at this pass's own size
-    const size_t per = (size_t)E->vj_ws_per_lane * sizeof(double);
-    if (E->vj_bt) {
-      const int per_cu = std::max(1, (int)((160 * 1024) / (per * E->vj_bt + 3 * 1024)));
-      hipLaunchKernelGGL(k_vcf_joint_es<true>, dim3(E->n_cu * per_cu * 2), dim3(E->vj_bt), per * E->vj_bt, E->stream, A, P);
-    } else
-      hipLaunchKernelGGL(k_vcf_joint_es<false>, dim3(E->vj_grid), dim3(256), 0, E->stream, A, P);
-    HIP_TRY(hipGetLastError());
-  }
-  return PM_OK;
+  return launch_plane_pass(E, A, P, lean, k_vcf_joint_lean, (size_t)E->n_fam * 4, k_vcf_joint_nuc, es, P.n_fams, k_vcf_joint_es<true>,
+                           k_vcf_joint_es<false>, es_block_shape(E, E->vj_ws_per_lane), E->vj_grid);
 }
 
 static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* dm, const uint8_t* ref, pm_site_result* res,
@@ -1393,28 +1408,22 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
       HIP_TRY(hipModuleLaunchKernel(K->fn_post, E->n_cu * 8, 1, 1, 256, 1, 1, 0, E->stream, params, nullptr));
     } else if (es && A.n_es_pers > 0) {
       HIP_TRY(hipGetLastError());
-      // LDS workspace when a 64-thread block's share fits: the block size is the largest of 256/128/64 whose
-      // workspace stays within the 64 KB default dynamic-LDS limit
-      const size_t per = (size_t)E->ws_per_lane * sizeof(double);
-      int bt = 0;
-      for (int t : {256, 128, 64})
-        if (!bt && per * t <= 64 * 1024 && !E->sw.es_post_hbm) bt = t;
-      if (bt) {
-        const int per_cu = std::max(1, (int)((160 * 1024) / (per * bt + 3 * 1024)));
+      const EsShape sh = es_block_shape(E, E->ws_per_lane);
+      if (sh.bt) {
         void (*pe)(DevArgs) = E->par.denovo ? k_posterior_es<true, true> : k_posterior_es<false, true>;
-        hipLaunchKernelGGL(pe, dim3(E->n_cu * per_cu * 2), dim3(bt), per * bt, E->stream, A);
+        hipLaunchKernelGGL(pe, dim3(sh.grid), dim3(sh.bt), sh.lds_bytes, E->stream, A);
       } else
-        hipLaunchKernelGGL(E->par.denovo ? k_posterior_es<true> : k_posterior_es<false>, dim3(E->grid_post), dim3(256), 0, E->stream, A);
+        hipLaunchKernelGGL(E->par.denovo ? k_posterior_es<true> : k_posterior_es<false>, dim3(sh.grid), dim3(256), 0, E->stream, A);
     }
-    if (E->vp_on) {
+    if (E->vp.on) {
       HIP_TRY(hipGetLastError());
       if ((rc = launch_vcf_posteriors(E, A, lean, es))) return rc;
     }
-    if (E->vph_on) {
+    if (E->vph.on) {
       HIP_TRY(hipGetLastError());
       if ((rc = launch_vcf_phase(E, A, lean, es))) return rc;
     }
-    if (E->vj_on) {
+    if (E->vj.on) {
       HIP_TRY(hipGetLastError());
       if ((rc = launch_vcf_joint(E, A, lean, es))) return rc;
     }
@@ -1610,99 +1619,91 @@ int pm_engine_set_vcf_denovo(pm_engine* E, int32_t on) {
   return PM_OK;
 }
 
-int pm_engine_set_vcf_posteriors(pm_engine* E, int32_t on) {
-  if (!E) { pm_set_last_error("pm_engine_set_vcf_posteriors: invalid arguments"); return PM_EINVAL; }
-  if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_posteriors: the engine was created without vcf_mode"); return PM_EINVAL; }
-  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_vcf_posteriors: a submitted batch has not been collected"); return PM_EINVAL; }
+// The output planes' setters and getters.  name: "vcf_phase" for pm_engine_set_vcf_phase / pm_engine_vcf_phase.
+static int plane_refuse(const char* fn_prefix, const char* name, const char* why, const char* why_arg = "") {
+  char b[192];
+  const int k = snprintf(b, sizeof(b), "%s%s: ", fn_prefix, name);
+  snprintf(b + k, sizeof(b) - k, why, why_arg);
+  pm_set_last_error(b);
+  return PM_EINVAL;
+}
+// A setter's guards, then the device selected and the stream idle
+static int plane_guard(pm_engine* E, const char* name) {
+  if (!E) return plane_refuse("pm_engine_set_", name, "invalid arguments");
+  if (!E->vcf) return plane_refuse("pm_engine_set_", name, "the engine was created without vcf_mode");
+  if (E->pending_n >= 0) return plane_refuse("pm_engine_set_", name, "a submitted batch has not been collected");
   HIP_TRY(hipSetDevice(E->device));
   HIP_TRY(hipStreamSynchronize(E->stream));
-  if (!on) {
-    E->vp_on = E->vp_valid = false;
-    if (E->d_vp) (void)hipFree(E->d_vp);
-    E->d_vp = nullptr;
-    return PM_OK;
-  }
-  if (E->vp_on) return PM_OK;   // (already on: the last batch's plane stays)
-  const size_t cells = (size_t)E->max_batch * E->n_person;   // max_batch x n_person x 12 bytes
-  if (int rc = dalloc(&E->d_vp, cells)) return rc;
-  HIP_TRY(hipMemset(E->d_vp, 0, cells * sizeof(pm_vcf_post)));
-  E->vp_on = true;
-  E->vp_valid = false;   // (no batch has filled it yet)
   return PM_OK;
+}
+static void plane_free(Plane& pl) {
+  pl.on = pl.valid = false;
+  dfree(&pl.d);
+}
+// max_batch x n_person cells, cleared; on, and no batch has filled it yet
+static int plane_alloc_clear(pm_engine* E, Plane& pl) {
+  const size_t bytes = (size_t)E->max_batch * E->n_person * pl.cell;
+  if (int rc = dalloc((char**)&pl.d, bytes)) return rc;
+  HIP_TRY(hipMemset(pl.d, 0, bytes));
+  pl.on = true;
+  pl.valid = false;
+  return PM_OK;
+}
+// The rows of the last finished batch (0 when it did not fill the plane) and, with out, their cells
+static int plane_fetch(pm_engine* E, Plane pm_engine::*which, const char* name, int32_t* n_rows, void* out) {
+  if (!E || !n_rows) return plane_refuse("pm_engine_", name, "invalid arguments");
+  const Plane& pl = E->*which;
+  if (!pl.on) return plane_refuse("pm_engine_", name, "the feature is off (pm_engine_set_%s)", name);
+  if (E->pending_n >= 0) return plane_refuse("pm_engine_", name, "a submitted batch has not been collected");
+  *n_rows = pl.valid ? E->last_rows : 0;
+  if (out && *n_rows > 0) {
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipMemcpy(out, pl.d, pl.cell * (size_t)*n_rows * E->n_person, hipMemcpyDeviceToHost));
+  }
+  return PM_OK;
+}
+
+int pm_engine_set_vcf_posteriors(pm_engine* E, int32_t on) {
+  if (int rc = plane_guard(E, "vcf_posteriors")) return rc;
+  if (!on) { plane_free(E->vp); return PM_OK; }
+  if (E->vp.on) return PM_OK;   // (already on: the last batch's plane stays)
+  return plane_alloc_clear(E, E->vp);
 }
 
 int pm_engine_vcf_posteriors(pm_engine* E, int32_t* n_rows, pm_vcf_post* out) {
-  if (!E || !n_rows) { pm_set_last_error("pm_engine_vcf_posteriors: invalid arguments"); return PM_EINVAL; }
-  if (!E->vp_on) { pm_set_last_error("pm_engine_vcf_posteriors: the feature is off (pm_engine_set_vcf_posteriors)"); return PM_EINVAL; }
-  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_vcf_posteriors: a submitted batch has not been collected"); return PM_EINVAL; }
-  *n_rows = E->vp_valid ? E->last_rows : 0;
-  if (out && *n_rows > 0) {
-    HIP_TRY(hipSetDevice(E->device));
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    HIP_TRY(hipMemcpy(out, E->d_vp, sizeof(pm_vcf_post) * (size_t)*n_rows * E->n_person, hipMemcpyDeviceToHost));
-  }
-  return PM_OK;
+  return plane_fetch(E, &pm_engine::vp, "vcf_posteriors", n_rows, out);
+}
+
+static void vph_off(pm_engine* E) {
+  plane_free(E->vph);
+  E->vph_kids.free();
 }
 
 int pm_engine_set_vcf_phase(pm_engine* E, int32_t on) {
-  if (!E) { pm_set_last_error("pm_engine_set_vcf_phase: invalid arguments"); return PM_EINVAL; }
-  if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_phase: the engine was created without vcf_mode"); return PM_EINVAL; }
-  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_vcf_phase: a submitted batch has not been collected"); return PM_EINVAL; }
-  HIP_TRY(hipSetDevice(E->device));
-  HIP_TRY(hipStreamSynchronize(E->stream));
-  if (!on) {
-    E->vph_on = E->vph_valid = false;
-    void** bufs[] = {(void**)&E->d_vph, (void**)&E->d_vph_kids[0], (void**)&E->d_vph_kids[1]};
-    for (void** b : bufs) {
-      if (*b) (void)hipFree(*b);
-      *b = nullptr;
-    }
-    return PM_OK;
-  }
-  if (E->vph_on) return PM_OK;   // (already on: the last batch's plane stays)
-  const size_t cells = (size_t)E->max_batch * E->n_person;   // max_batch x n_person x 8 bytes
-  if (int rc = dalloc(&E->d_vph, cells)) return rc;
-  HIP_TRY(hipMemset(E->d_vph, 0, cells * sizeof(pm_vcf_phase)));   // (the founders of peeled families are never written)
-  for (int plan = 0; plan < 2; plan++) {
-    const std::vector<int>& k = E->vph_kids_h[plan];
-    if (int rc = dalloc(&E->d_vph_kids[plan], std::max<size_t>(1, k.size()))) return rc;
-    if (!k.empty()) HIP_TRY(hipMemcpy(E->d_vph_kids[plan], k.data(), sizeof(int) * k.size(), hipMemcpyHostToDevice));
-  }
-  E->vph_on = true;
-  E->vph_valid = false;   // (no batch has filled it yet)
-  return PM_OK;
+  if (int rc = plane_guard(E, "vcf_phase")) return rc;
+  if (!on) { vph_off(E); return PM_OK; }
+  if (E->vph.on) return PM_OK;   // (already on: the last batch's plane stays)
+  int rc = plane_alloc_clear(E, E->vph);   // (cleared: the founders of peeled families are never written)
+  if (!rc) rc = E->vph_kids.upload();
+  if (rc) vph_off(E);
+  return rc;
 }
 
 int pm_engine_vcf_phase(pm_engine* E, int32_t* n_rows, pm_vcf_phase* out) {
-  if (!E || !n_rows) { pm_set_last_error("pm_engine_vcf_phase: invalid arguments"); return PM_EINVAL; }
-  if (!E->vph_on) { pm_set_last_error("pm_engine_vcf_phase: the feature is off (pm_engine_set_vcf_phase)"); return PM_EINVAL; }
-  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_vcf_phase: a submitted batch has not been collected"); return PM_EINVAL; }
-  *n_rows = E->vph_valid ? E->last_rows : 0;
-  if (out && *n_rows > 0) {
-    HIP_TRY(hipSetDevice(E->device));
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    HIP_TRY(hipMemcpy(out, E->d_vph, sizeof(pm_vcf_phase) * (size_t)*n_rows * E->n_person, hipMemcpyDeviceToHost));
-  }
-  return PM_OK;
+  return plane_fetch(E, &pm_engine::vph, "vcf_phase", n_rows, out);
 }
 
-static void vj_free(pm_engine* E) {
-  E->vj_on = E->vj_valid = false;
-  void** bufs[] = {(void**)&E->d_vj, (void**)&E->d_vj_fams[0], (void**)&E->d_vj_fams[1], (void**)&E->d_vj_ws};
-  for (void** b : bufs) {
-    if (*b) (void)hipFree(*b);
-    *b = nullptr;
-  }
+static void vj_off(pm_engine* E) {
+  plane_free(E->vj);
+  E->vj_fams.free();
+  dfree((void**)&E->d_vj_ws);
 }
 
 int pm_engine_set_vcf_joint(pm_engine* E, int32_t on) {
-  if (!E) { pm_set_last_error("pm_engine_set_vcf_joint: invalid arguments"); return PM_EINVAL; }
-  if (!E->vcf) { pm_set_last_error("pm_engine_set_vcf_joint: the engine was created without vcf_mode"); return PM_EINVAL; }
-  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_set_vcf_joint: a submitted batch has not been collected"); return PM_EINVAL; }
-  HIP_TRY(hipSetDevice(E->device));
-  HIP_TRY(hipStreamSynchronize(E->stream));
-  if (!on) { vj_free(E); return PM_OK; }
-  if (E->vj_on) return PM_OK;   // (already on: the last batch's plane stays)
+  if (int rc = plane_guard(E, "vcf_joint")) return rc;
+  if (!on) { vj_off(E); return PM_OK; }
+  if (E->vj.on) return PM_OK;   // (already on: the last batch's plane stays)
   // the max peel's workspace per thread: a back-pointer word per step on top of the partials [n][3] and the marriage
   // partials [slots][9] that ws_per_lane covers (the sum peel for L runs in the same words)
   int ws_need = E->ws_per_lane;
@@ -1717,38 +1718,19 @@ int pm_engine_set_vcf_joint(pm_engine* E, int32_t on) {
     ws_need = std::max(ws_need, (E->fam_start_h[f + 1] - E->fam_start_h[f]) * 3 + slots * 9 + (s1 - s0));
   }
   E->vj_ws_per_lane = ws_need;
+  // its HBM form's grid: grid_post blocks, fewer where their workspace would pass 1 GiB, never below one
   const size_t per = (size_t)ws_need * sizeof(double);
-  E->vj_bt = 0;
-  for (int t : {256, 128, 64})
-    if (!E->vj_bt && per * t <= 64 * 1024 && !E->sw.es_post_hbm) E->vj_bt = t;
   E->vj_grid = per ? (int)std::max<size_t>(1, std::min<size_t>(E->grid_post, ((size_t)1 << 30) / (per * 256))) : E->grid_post;
-  const size_t cells = (size_t)E->max_batch * E->n_person;   // max_batch x n_person x 8 bytes
-  int rc = dalloc(&E->d_vj, cells);
-  const bool peels = !E->vj_fams_h[0].empty() || !E->vj_fams_h[1].empty();
-  if (!rc && peels && !E->vj_bt) rc = dalloc(&E->d_vj_ws, (size_t)E->vj_grid * 256 * ws_need);
-  for (int plan = 0; plan < 2 && !rc; plan++) {
-    const std::vector<int>& k = E->vj_fams_h[plan];
-    rc = dalloc(&E->d_vj_fams[plan], std::max<size_t>(1, k.size()));
-    if (!rc && !k.empty() && hipMemcpy(E->d_vj_fams[plan], k.data(), sizeof(int) * k.size(), hipMemcpyHostToDevice) != hipSuccess) rc = PM_EHIP;
-  }
-  if (!rc && hipMemset(E->d_vj, 0, cells * sizeof(pm_vcf_joint)) != hipSuccess) rc = PM_EHIP;
-  if (rc) { vj_free(E); return rc; }
-  E->vj_on = true;
-  E->vj_valid = false;   // (no batch has filled it yet)
-  return PM_OK;
+  const bool peels = !E->vj_fams.h[0].empty() || !E->vj_fams.h[1].empty();
+  int rc = plane_alloc_clear(E, E->vj);
+  if (!rc && peels && !es_block_shape(E, ws_need).bt) rc = dalloc(&E->d_vj_ws, (size_t)E->vj_grid * 256 * ws_need);
+  if (!rc) rc = E->vj_fams.upload();
+  if (rc) vj_off(E);
+  return rc;
 }
 
 int pm_engine_vcf_joint(pm_engine* E, int32_t* n_rows, pm_vcf_joint* out) {
-  if (!E || !n_rows) { pm_set_last_error("pm_engine_vcf_joint: invalid arguments"); return PM_EINVAL; }
-  if (!E->vj_on) { pm_set_last_error("pm_engine_vcf_joint: the feature is off (pm_engine_set_vcf_joint)"); return PM_EINVAL; }
-  if (E->pending_n >= 0) { pm_set_last_error("pm_engine_vcf_joint: a submitted batch has not been collected"); return PM_EINVAL; }
-  *n_rows = E->vj_valid ? E->last_rows : 0;
-  if (out && *n_rows > 0) {
-    HIP_TRY(hipSetDevice(E->device));
-    HIP_TRY(hipStreamSynchronize(E->stream));
-    HIP_TRY(hipMemcpy(out, E->d_vj, sizeof(pm_vcf_joint) * (size_t)*n_rows * E->n_person, hipMemcpyDeviceToHost));
-  }
-  return PM_OK;
+  return plane_fetch(E, &pm_engine::vj, "vcf_joint", n_rows, out);
 }
 
 int pm_engine_set_vcf_denovo_chrx(pm_engine* E, int32_t on) {

@@ -9,10 +9,10 @@
 // max J = 0 or L = 0 gives g = 255 and lp = 0.  Included by engine.hip after vcf_phase_dev.h.
 //
 // One extra pass after the phase plane's, on the engine's stream, only with the feature on.  Its kernels write the plane
-// (VjArgs::joint, [row][person] of pm_vcf_joint) and nothing else.  They are chosen as vcf_phase_dev.h's are:
-//   k_vcf_joint_lean  nuclear families of <= 4 persons and founders-only families (k_vcf_phase_lean's case and loop);
-//   k_vcf_joint_nuc   every other closed-form nuclear family, one thread per (row, family);
-//   k_vcf_joint_es    peeled families, one thread per (row, family): d_es_joint3, the autosomal three-state peel with max in
+// (VjArgs::joint, [row][person] of pm_vcf_joint) and nothing else, one kernel per loop of vcf_plane_dev.h:
+//   k_vcf_joint_lean  lean_nuc_joint, the argmax over the parental pairs from a family's 12 PL bytes;
+//   k_vcf_joint_nuc   the same argmax with the product over any number of kids;
+//   k_vcf_joint_es    one thread per (row, peeled family): d_es_joint3, the autosomal three-state peel with max in
 //                     place of every sum and a back-pointer word per step, then a backtrack through the steps in reverse.
 // Ties go to the first maximum of the fixed enumeration order (a candidate replaces the best only when strictly greater).
 // No atomics, no scratch; lp is formed in double and rounded once to float.  Sections that are not autosomal launch
@@ -129,105 +129,72 @@ __device__ __forceinline__ void lean_nuc_joint(const double* s_lk, const uint32_
   if (two) d_store_joint(vj + out + p0 + 3, ok ? gb1 : 255, lp);
 }
 
-// k_vcf_phase_lean's loop: a block per emitted row at a time, its threads striding over the families in fam_perm order,
-// the family table in LDS, the next row's set-up loaded under this row's arithmetic.  A lane owns a family: its persons are
-// contiguous and adjacent lanes hold adjacent families, so a wave writes one contiguous stretch of the plane, 8 bytes per
-// person at a time.
+// The lean loop around lean_nuc_joint and d_joint_founders, 8 bytes per person at a time.
 __global__ void __launch_bounds__(256) k_vcf_joint_lean(DevArgs A, VjArgs P) {
   __shared__ double s_lk[256];
   extern __shared__ uint32_t s_fam[];   // [n_fam]
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lk[i] = A.lktab[i];
-  for (int fi = threadIdx.x; fi < A.n_fam; fi += blockDim.x) {
-    const int f = A.fam_perm[fi];
-    const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0;
-    s_fam[fi] = (uint32_t)p0 | (uint32_t)n << 24 | (A.fam_kind[f] == PM_FAM_NUCLEAR ? 1u << 31 : 0u);
-  }
+  stage_lk(s_lk, A);
+  lean_fam_table(A, s_fam);
   __syncthreads();
-  const int rows = A.counts[3], np = A.n_person, nf = A.n_fam;
-  int row = blockIdx.x;
-  if (row >= rows || (int)threadIdx.x >= nf) return;
-  LeanRow cur, nxt;
-  lean_row(A, row, cur);
-  for (; row < rows; row += gridDim.x) {
-    if (row + (int)gridDim.x < rows) lean_row(A, row + gridDim.x, nxt);
-    double pp[9];
-    d_parent_prior((!A.n_fam_gt1 && !cur.mono) ? PR_TRIO : PR_AUTO, cur.freq, pp);
-    for (int fi = threadIdx.x; fi < nf; fi += blockDim.x) {
-      const uint32_t d = s_fam[fi];
-      const int p0 = d & 0xFFFFFF, n = (d >> 24) & 127;
-      if (d >> 31) {
-        uint32_t by[12];
-        lean_fam_bytes(cur.pl, np, p0, n, cur.g11, cur.g12, cur.g22, by);
-        const int n0 = __builtin_amdgcn_readfirstlane(n);
-        const bool uni = __builtin_amdgcn_ballot_w64(n != n0) == 0;
-        if (uni && n0 == 4) lean_nuc_joint<4>(s_lk, by, cur.out, p0, n, pp, P.joint);
-        else if (uni && n0 == 3) lean_nuc_joint<3>(s_lk, by, cur.out, p0, n, pp, P.joint);
-        else lean_nuc_joint<0>(s_lk, by, cur.out, p0, n, pp, P.joint);
-      } else {
-        d_joint_founders(s_lk, cur.pl, np, p0, n, cur.g11, cur.g12, cur.g22, cur.freq, P.joint + cur.out);
-      }
-    }
-    cur = nxt;
-  }
+  lean_family_rows(
+      A, s_fam,
+      [&](auto nf, const LeanRow& cur, const double* pp, int, int p0, int n, const uint32_t* by) {
+        lean_nuc_joint<decltype(nf)::value>(s_lk, by, cur.out, p0, n, pp, P.joint);
+      },
+      [&](const LeanRow& cur, int p0, int n) {
+        d_joint_founders(s_lk, cur.pl, A.n_person, p0, n, cur.g11, cur.g12, cur.g22, cur.freq, P.joint + cur.out);
+      });
 }
 
-// One thread per (row, family) in fam_perm order: founders-only families factorise; a nuclear family of any number of
-// children takes lean_nuc_joint's argmax with the product over its kids, kid by kid in person order, and a second pass
-// over the kids for their states under the best pair.  Families the section peels are k_vcf_joint_es's.
+// The nuc loop: founders-only families factorise; a nuclear family of any number of children takes lean_nuc_joint's argmax
+// with the product over its kids, kid by kid in person order, and a second pass over the kids for their states under the
+// best pair.
 __global__ void __launch_bounds__(256) k_vcf_joint_nuc(DevArgs A, VjArgs P) {
   __shared__ double s_lk[256];
   __shared__ double s_tba[27];
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lk[i] = A.lktab[i];
-  if (threadIdx.x < 27) s_tba[threadIdx.x] = c_TBA[0][threadIdx.x];
+  stage_lk(s_lk, A);
+  stage_tba(s_tba);
   __syncthreads();
-  const long long work = (long long)A.counts[3] * A.n_fam;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x; gid < work; gid += stride) {
-    const int row = (int)(gid / A.n_fam), f = A.fam_perm[(int)(gid % A.n_fam)];
-    LeanRow r;
-    lean_row(A, row, r);
-    const int np = A.n_person;
-    const uint8_t* pl = r.pl;
-    const int g11 = r.g11, g12 = r.g12, g22 = r.g22;
-    const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0, kind = A.fam_kind[f];
-    pm_vcf_joint* out = P.joint + r.out;
-    if (kind == PM_FAM_FOUNDERS) {
-      d_joint_founders(s_lk, pl, np, p0, n, g11, g12, g22, r.freq, out);
-      continue;
-    }
-    if (kind != PM_FAM_NUCLEAR || A.nuc_es) continue;   // peeled: k_vcf_joint_es
-    double pp[9];
-    d_parent_prior((!A.n_fam_gt1 && !r.mono) ? PR_TRIO : PR_AUTO, r.freq, pp);
-    const double F0 = s_lk[PLB(pl, np, p0, g11)], F1 = s_lk[PLB(pl, np, p0, g12)], F2 = s_lk[PLB(pl, np, p0, g22)];
-    const double M0 = s_lk[PLB(pl, np, p0 + 1, g11)], M1 = s_lk[PLB(pl, np, p0 + 1, g12)], M2 = s_lk[PLB(pl, np, p0 + 1, g22)];
-    double best = 0.0, L = 0.0;
-    int kb = -1;
+  const int np = A.n_person;
+  nuc_family_rows(
+      A,
+      [&](const LeanRow& r, int p0, int n) { d_joint_founders(s_lk, r.pl, np, p0, n, r.g11, r.g12, r.g22, r.freq, P.joint + r.out); },
+      [&](const LeanRow& r, int, int, int p0, int n) {
+        const uint8_t* pl = r.pl;
+        const int g11 = r.g11, g12 = r.g12, g22 = r.g22;
+        pm_vcf_joint* out = P.joint + r.out;
+        double pp[9];
+        d_parent_prior((!A.n_fam_gt1 && !r.mono) ? PR_TRIO : PR_AUTO, r.freq, pp);
+        const double F0 = s_lk[PLB(pl, np, p0, g11)], F1 = s_lk[PLB(pl, np, p0, g12)], F2 = s_lk[PLB(pl, np, p0, g22)];
+        const double M0 = s_lk[PLB(pl, np, p0 + 1, g11)], M1 = s_lk[PLB(pl, np, p0 + 1, g12)], M2 = s_lk[PLB(pl, np, p0 + 1, g22)];
+        double best = 0.0, L = 0.0;
+        int kb = -1;
 #pragma unroll
-    for (int k = 0; k < 9; k++) {
-      const double lf = k / 3 == 0 ? F0 : k / 3 == 1 ? F1 : F2, lm = k % 3 == 0 ? M0 : k % 3 == 1 ? M1 : M2;
-      const double w = (lf * lm) * pp[k];
-      double sc = w, sm = w;
-      for (int j = 2; j < n; j++) {
-        double s, m;
-        int g;
-        d_joint_kid(s_tba + 3 * k, s_lk[PLB(pl, np, p0 + j, g11)], s_lk[PLB(pl, np, p0 + j, g12)], s_lk[PLB(pl, np, p0 + j, g22)], s, m, g);
-        sc *= m; sm *= s;
-      }
-      L = k == 0 ? sm : L + sm;
-      if (sc > best) { best = sc; kb = k; }
-    }
-    const bool ok = kb >= 0 && L > 0.0;
-    const double lp = ok ? log10(best / L) : 0.0;
-    d_store_joint(out + p0, ok ? kb / 3 : 255, lp);
-    d_store_joint(out + p0 + 1, ok ? kb % 3 : 255, lp);
-    const double* tk = s_tba + 3 * (ok ? kb : 0);
-    for (int j = 2; j < n; j++) {
-      double s, m;
-      int g;
-      d_joint_kid(tk, s_lk[PLB(pl, np, p0 + j, g11)], s_lk[PLB(pl, np, p0 + j, g12)], s_lk[PLB(pl, np, p0 + j, g22)], s, m, g);
-      d_store_joint(out + p0 + j, ok ? g : 255, lp);
-    }
-  }
+        for (int k = 0; k < 9; k++) {
+          const double lf = k / 3 == 0 ? F0 : k / 3 == 1 ? F1 : F2, lm = k % 3 == 0 ? M0 : k % 3 == 1 ? M1 : M2;
+          const double w = (lf * lm) * pp[k];
+          double sc = w, sm = w;
+          for (int j = 2; j < n; j++) {
+            double s, m;
+            int g;
+            d_joint_kid(s_tba + 3 * k, s_lk[PLB(pl, np, p0 + j, g11)], s_lk[PLB(pl, np, p0 + j, g12)], s_lk[PLB(pl, np, p0 + j, g22)], s, m, g);
+            sc *= m; sm *= s;
+          }
+          L = k == 0 ? sm : L + sm;
+          if (sc > best) { best = sc; kb = k; }
+        }
+        const bool ok = kb >= 0 && L > 0.0;
+        const double lp = ok ? log10(best / L) : 0.0;
+        d_store_joint(out + p0, ok ? kb / 3 : 255, lp);
+        d_store_joint(out + p0 + 1, ok ? kb % 3 : 255, lp);
+        const double* tk = s_tba + 3 * (ok ? kb : 0);
+        for (int j = 2; j < n; j++) {
+          double s, m;
+          int g;
+          d_joint_kid(tk, s_lk[PLB(pl, np, p0 + j, g11)], s_lk[PLB(pl, np, p0 + j, g12)], s_lk[PLB(pl, np, p0 + j, g22)], s, m, g);
+          d_store_joint(out + p0 + j, ok ? g : 255, lp);
+        }
+      });
 }
 
 // d_es_lk3_vdn's autosomal peel (both tables the plain transmission tt, nobody clamped) with max in place of every sum and a
@@ -338,28 +305,20 @@ __device__ __forceinline__ void d_es_joint3(const DevArgs& A, int f, const uint8
 #undef MPP
 }
 
-// One thread per (row, peeled family): one unclamped sum peel for the normaliser L (d_es_lk3_vdn<false>, both of its tables
-// the plain transmission in LDS, as k_vcf_phase_es takes it), then the max peel and its backtrack over the same workspace.
-// LDSWS as k_vcf_phase_es's: the workspace in dynamic LDS, interleaved across the block's threads, instead of the
-// lane-interleaved HBM one (VjArgs::ws, this pass's own: the back-pointers need more words than DevArgs::ws has per lane).
+// The es loop over the peeled families (VjArgs::fams): one unclamped sum peel for the normaliser L (d_es_lk3_vdn<false>,
+// both of its tables the plain transmission in LDS, as k_vcf_phase_es takes it), then the max peel and its backtrack over
+// the same workspace.  The HBM workspace is VjArgs::ws, this pass's own: the back-pointers need more words than DevArgs::ws
+// has per lane.
 template <bool LDSWS>
 __global__ void __launch_bounds__(256) k_vcf_joint_es(DevArgs A, VjArgs P) {
   __shared__ double s_lk[256];
   __shared__ double s_tba[27];
-  extern __shared__ double s_wsp[];
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lk[i] = A.lktab[i];
-  if (threadIdx.x < 27) s_tba[threadIdx.x] = c_TBA[0][threadIdx.x];
+  stage_lk(s_lk, A);
+  stage_tba(s_tba);
   __syncthreads();
-  const long long work = (long long)A.counts[3] * P.n_fams;
-  const size_t gid_base = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = LDSWS ? (size_t)blockDim.x : (size_t)gridDim.x * blockDim.x;   // workspace stride
-  double* wsl = LDSWS ? s_wsp + threadIdx.x : P.ws + gid_base;
-  for (long long gid = (long long)gid_base; gid < work; gid += (long long)gridDim.x * blockDim.x) {
-    const int row = (int)(gid / P.n_fams), f = P.fams[gid % P.n_fams];
-    LeanRow r;
-    lean_row(A, row, r);
+  es_rows<LDSWS>(A, P.ws, P.fams, P.n_fams, [&](const LeanRow& r, int f, double* wsl, size_t stride) {
     const int gidx[3] = {r.g11, r.g12, r.g22};
     const double L = d_es_lk3_vdn<false>(A, f, r.pl, s_lk, gidx, r.freq, s_tba, s_tba, wsl, stride);
     d_es_joint3(A, f, r.pl, s_lk, gidx, r.freq, s_tba, wsl, stride, L, P.joint + r.out);
-  }
+  });
 }

@@ -9,12 +9,10 @@
 // Founders get (0, 0), and so does a person whose normalising sum is zero.  Included by engine.hip after vcf_post_dev.h.
 //
 // One extra pass after the standard posterior stage (and after the posterior plane's pass), on the engine's stream, only
-// with the feature on.  Its kernels write the plane (VphArgs::phase, [row][person] of pm_vcf_phase) and nothing else.  They
-// are chosen as vcf_post_dev.h's are:
-//   k_vcf_phase_lean  nuclear families of <= 4 persons and founders-only families (k_vcf_post_lean's case and loop) around a
-//                     body of its own, lean_nuc_phase: lean_nuc_post's kid terms with the het ones split by (a, b);
-//   k_vcf_phase_nuc   every other closed-form nuclear family: hoist-free, d_parent_prior and d_kid_geno in
-//                     k_vcf_post_nuc's order with the same split;
+// with the feature on.  Its kernels write the plane (VphArgs::phase, [row][person] of pm_vcf_phase) and nothing else, one
+// kernel per loop of vcf_plane_dev.h:
+//   k_vcf_phase_lean  lean_nuc_phase: lean_nuc_post's kid terms with the het ones split by (a, b);
+//   k_vcf_phase_nuc   hoist-free, d_parent_prior and d_kid_geno in k_vcf_post_nuc's order with the same split;
 //   k_vcf_phase_es    the children of peeled families: seven d_es_lk3_vdn<true> peels with father, mother and child (het)
 //                     clamped, both tables the plain transmission, and one unclamped peel for L.
 // Fixed summation order, no atomics, no scratch; a value is the double quotient rounded once to float.  Sections that are
@@ -97,132 +95,91 @@ __device__ __forceinline__ void lean_nuc_phase(const double* s_lk, const uint32_
   }
 }
 
-// k_vcf_post_lean's loop: a block per emitted row at a time, its threads striding over the families in fam_perm order,
-// the family table in LDS, the next row's set-up loaded under this row's arithmetic.  Behind the packed family table the
-// dynamic LDS holds a byte per family: which of its kid slots have person p0 + 1 as father (n_fam * 5 bytes in all).  A lane
-// owns a family: its 3 or 4 persons are contiguous and adjacent lanes hold adjacent families, so a wave writes one
-// contiguous stretch of the plane, 8 bytes per person at a time.
+// The lean loop around lean_nuc_phase, 8 bytes per person at a time.  Behind the packed family table the dynamic LDS holds
+// a byte per family: which of its kid slots have person p0 + 1 as father (n_fam * 5 bytes in all).
 __global__ void __launch_bounds__(256) k_vcf_phase_lean(DevArgs A, VphArgs P) {
   __shared__ double s_lk[256];
   extern __shared__ uint32_t s_fam[];   // [n_fam], then uint8_t [n_fam]
   uint8_t* s_sw = reinterpret_cast<uint8_t*>(s_fam + A.n_fam);
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lk[i] = A.lktab[i];
-  for (int fi = threadIdx.x; fi < A.n_fam; fi += blockDim.x) {
-    const int f = A.fam_perm[fi];
-    const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0;
-    const bool nuc = A.fam_kind[f] == PM_FAM_NUCLEAR;
-    s_fam[fi] = (uint32_t)p0 | (uint32_t)n << 24 | (nuc ? 1u << 31 : 0u);
+  stage_lk(s_lk, A);
+  lean_fam_table(A, s_fam, [&](int fi, int, int p0, int n, bool nuc) {
     unsigned m = 0;
     if (nuc)
       for (int j = 2; j < n && j < 4; j++) m |= (A.fa_local[p0 + j] == 1 ? 1u : 0u) << (j - 2);
     s_sw[fi] = (uint8_t)m;
-  }
+  });
   __syncthreads();
-  const int rows = A.counts[3], np = A.n_person, nf = A.n_fam;
-  int row = blockIdx.x;
-  if (row >= rows || (int)threadIdx.x >= nf) return;
-  LeanRow cur, nxt;
-  lean_row(A, row, cur);
-  for (; row < rows; row += gridDim.x) {
-    if (row + (int)gridDim.x < rows) lean_row(A, row + gridDim.x, nxt);
-    double pp[9];
-    d_parent_prior((!A.n_fam_gt1 && !cur.mono) ? PR_TRIO : PR_AUTO, cur.freq, pp);
-    for (int fi = threadIdx.x; fi < nf; fi += blockDim.x) {
-      const uint32_t d = s_fam[fi];
-      const int p0 = d & 0xFFFFFF, n = (d >> 24) & 127;
-      if (d >> 31) {
-        uint32_t by[12];
-        lean_fam_bytes(cur.pl, np, p0, n, cur.g11, cur.g12, cur.g22, by);
-        const unsigned swm = s_sw[fi];
-        const int n0 = __builtin_amdgcn_readfirstlane(n);
-        const bool uni = __builtin_amdgcn_ballot_w64(n != n0) == 0;
-        if (uni && n0 == 4) lean_nuc_phase<4>(s_lk, by, cur.out, p0, n, pp, swm, P.phase);
-        else if (uni && n0 == 3) lean_nuc_phase<3>(s_lk, by, cur.out, p0, n, pp, swm, P.phase);
-        else lean_nuc_phase<0>(s_lk, by, cur.out, p0, n, pp, swm, P.phase);
-      } else {
+  lean_family_rows(
+      A, s_fam,
+      [&](auto nf, const LeanRow& cur, const double* pp, int fi, int p0, int n, const uint32_t* by) {
+        lean_nuc_phase<decltype(nf)::value>(s_lk, by, cur.out, p0, n, pp, s_sw[fi], P.phase);
+      },
+      [&](const LeanRow& cur, int p0, int n) {
         for (int j = 0; j < n; j++) d_store_phase(P.phase + cur.out + p0 + j, 0.0, 0.0, 0.0);   // founders only
-      }
-    }
-    cur = nxt;
-  }
+      });
 }
 
-// One thread per (row, family) in fam_perm order, k_vcf_post_nuc's arithmetic on an autosome: founders-only families are
-// zeros; a nuclear family's children take KidJointGenoLikelihood's nine terms J[k] * (pg[k] * pp[k]) in k order, the het
-// ones split by k.  Families the section peels are k_vcf_phase_es's (their founders are never written: the plane is
-// cleared when it is allocated and on sections that are not autosomal).
+// The nuc loop, k_vcf_post_nuc's arithmetic on an autosome: founders-only families are zeros; a nuclear family's children
+// take KidJointGenoLikelihood's nine terms J[k] * (pg[k] * pp[k]) in k order, the het ones split by k.  (The founders of
+// the families the section peels are never written: the plane is cleared when it is allocated and on sections that are
+// not autosomal.)
 __global__ void __launch_bounds__(256) k_vcf_phase_nuc(DevArgs A, VphArgs P) {
   __shared__ double s_lk[256];
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lk[i] = A.lktab[i];
+  stage_lk(s_lk, A);
   __syncthreads();
-  const long long work = (long long)A.counts[3] * A.n_fam;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x; gid < work; gid += stride) {
-    const int row = (int)(gid / A.n_fam), f = A.fam_perm[(int)(gid % A.n_fam)];
-    LeanRow r;
-    lean_row(A, row, r);
-    const int np = A.n_person;
-    const uint8_t* pl = r.pl;
-    const int g11 = r.g11, g12 = r.g12, g22 = r.g22;
-    const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0, kind = A.fam_kind[f];
-    pm_vcf_phase* out = P.phase + r.out;
-    if (kind == PM_FAM_FOUNDERS) {
-      for (int j = 0; j < n; j++) d_store_phase(out + p0 + j, 0.0, 0.0, 0.0);
-      continue;
-    }
-    if (kind != PM_FAM_NUCLEAR || A.nuc_es) continue;   // peeled: k_vcf_phase_es
-    double pp[9], wk[9];
-    d_parent_prior((!A.n_fam_gt1 && !r.mono) ? PR_TRIO : PR_AUTO, r.freq, pp);
-    {
-      const double lF[3] = {s_lk[PLB(pl, np, p0, g11)], s_lk[PLB(pl, np, p0, g12)], s_lk[PLB(pl, np, p0, g22)]};
-      const double lM[3] = {s_lk[PLB(pl, np, p0 + 1, g11)], s_lk[PLB(pl, np, p0 + 1, g12)], s_lk[PLB(pl, np, p0 + 1, g22)]};
+  nuc_family_rows(
+      A,
+      [&](const LeanRow& r, int p0, int n) {
+        for (int j = 0; j < n; j++) d_store_phase(P.phase + r.out + p0 + j, 0.0, 0.0, 0.0);
+      },
+      [&](const LeanRow& r, int, int, int p0, int n) {
+        const int np = A.n_person;
+        const uint8_t* pl = r.pl;
+        const int g11 = r.g11, g12 = r.g12, g22 = r.g22;
+        pm_vcf_phase* out = P.phase + r.out;
+        double pp[9], wk[9];
+        d_parent_prior((!A.n_fam_gt1 && !r.mono) ? PR_TRIO : PR_AUTO, r.freq, pp);
+        {
+          const double lF[3] = {s_lk[PLB(pl, np, p0, g11)], s_lk[PLB(pl, np, p0, g12)], s_lk[PLB(pl, np, p0, g22)]};
+          const double lM[3] = {s_lk[PLB(pl, np, p0 + 1, g11)], s_lk[PLB(pl, np, p0 + 1, g12)], s_lk[PLB(pl, np, p0 + 1, g22)]};
 #pragma unroll
-      for (int x = 0; x < 3; x++)
+          for (int x = 0; x < 3; x++)
 #pragma unroll
-        for (int y = 0; y < 3; y++) wk[3 * x + y] = (lF[x] * lM[y]) * pp[3 * x + y];   // pg[k] * pp[k]
-    }
-    d_store_phase(out + p0, 0.0, 0.0, 0.0);
-    d_store_phase(out + p0 + 1, 0.0, 0.0, 0.0);
-    for (int j = 2; j < n; j++) {
-      double q11 = 0.0, q12 = 0.0, q22 = 0.0, v[9];
+            for (int y = 0; y < 3; y++) wk[3 * x + y] = (lF[x] * lM[y]) * pp[3 * x + y];   // pg[k] * pp[k]
+        }
+        d_store_phase(out + p0, 0.0, 0.0, 0.0);
+        d_store_phase(out + p0 + 1, 0.0, 0.0, 0.0);
+        for (int j = 2; j < n; j++) {
+          double q11 = 0.0, q12 = 0.0, q22 = 0.0, v[9];
 #pragma unroll
-      for (int k = 0; k < 9; k++) {
-        double J[3];
-        d_kid_geno(PM_CHR_AUTO, pl, np, s_lk, p0, n, A.sex, g11, g12, g22, j, k, J);
-        const double w = wk[k];
-        J[0] *= w; J[1] *= w; J[2] *= w;
-        v[k] = J[1];
-        q11 = k == 0 ? J[0] : q11 + J[0]; q12 = k == 0 ? J[1] : q12 + J[1]; q22 = k == 0 ? J[2] : q22 + J[2];
-      }
-      double n12, n21;
-      d_phase_split(v, A.fa_local[p0 + j] == 1, n12, n21);
-      d_store_phase(out + p0 + j, q11 + q12 + q22, n12, n21);
-    }
-  }
+          for (int k = 0; k < 9; k++) {
+            double J[3];
+            d_kid_geno(PM_CHR_AUTO, pl, np, s_lk, p0, n, A.sex, g11, g12, g22, j, k, J);
+            const double w = wk[k];
+            J[0] *= w; J[1] *= w; J[2] *= w;
+            v[k] = J[1];
+            q11 = k == 0 ? J[0] : q11 + J[0]; q12 = k == 0 ? J[1] : q12 + J[1]; q22 = k == 0 ? J[2] : q22 + J[2];
+          }
+          double n12, n21;
+          d_phase_split(v, A.fa_local[p0 + j] == 1, n12, n21);
+          d_store_phase(out + p0 + j, q11 + q12 + q22, n12, n21);
+        }
+      });
 }
 
-// One thread per (row, non-founder of a peeled family): the seven (a, b) pairs with T[a][b][1] != 0, each one clamped
-// three-state peel in the reference's operation order with father = a, mother = b, child = het (d_es_lk3_vdn<true>, both of
-// its tables the plain transmission in LDS: d_es_lk<3>'s autosomal arithmetic), and one unclamped peel for the family
-// likelihood.  LDSWS as k_vcf_post_es's: the peel workspace in dynamic LDS, interleaved across the block's threads, instead
-// of the lane-interleaved HBM workspace (DevArgs::ws, idle once the standard stage's kernels are done on the stream).
+// The es loop over the non-founders of the peeled families (VphArgs::kids) and DevArgs::ws: the seven (a, b) pairs with
+// T[a][b][1] != 0, each one clamped three-state peel in the reference's operation order with father = a, mother = b, child =
+// het (d_es_lk3_vdn<true>, both of its tables the plain transmission in LDS: d_es_lk<3>'s autosomal arithmetic), and one
+// unclamped peel for the family likelihood.
 template <bool LDSWS>
 __global__ void __launch_bounds__(256) k_vcf_phase_es(DevArgs A, VphArgs P) {
   __shared__ double s_lk[256];
   __shared__ double s_tba[27];
-  extern __shared__ double s_wsp[];
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lk[i] = A.lktab[i];
-  if (threadIdx.x < 27) s_tba[threadIdx.x] = c_TBA[0][threadIdx.x];
+  stage_lk(s_lk, A);
+  stage_tba(s_tba);
   __syncthreads();
-  const long long work = (long long)A.counts[3] * P.n_kids;
-  const size_t gid_base = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = LDSWS ? (size_t)blockDim.x : (size_t)gridDim.x * blockDim.x;   // workspace stride
-  double* wsl = LDSWS ? s_wsp + threadIdx.x : A.ws + gid_base;
-  for (long long gid = (long long)gid_base; gid < work; gid += (long long)gridDim.x * blockDim.x) {
-    const int row = (int)(gid / P.n_kids), e = P.kids[gid % P.n_kids];
+  es_rows<LDSWS>(A, A.ws, P.kids, P.n_kids, [&](const LeanRow& r, int e, double* wsl, size_t stride) {
     const int f = e >> 8, jc = e & 255;
-    LeanRow r;
-    lean_row(A, row, r);
     const int p0 = A.fam_start[f], fa = A.fa_local[p0 + jc], mo = A.mo_local[p0 + jc];
     const int gidx[3] = {r.g11, r.g12, r.g22};
     // d_phase_split's sums with a = the father's state, taken as the peels come: k = 1, 2, 4, 5 into n12 and k = 3, 4, 6, 7
@@ -237,5 +194,5 @@ __global__ void __launch_bounds__(256) k_vcf_phase_es(DevArgs A, VphArgs P) {
     }
     const double L = d_es_lk3_vdn<false>(A, f, r.pl, s_lk, gidx, r.freq, s_tba, s_tba, wsl, stride);
     d_store_phase(P.phase + r.out + p0 + jc, L, n12, n21);
-  }
+  });
 }

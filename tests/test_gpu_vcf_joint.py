@@ -32,8 +32,9 @@ import polymutt_amd as pm
 from conftest import EXAMPLE
 from parity import DOSE_ATOL
 from test_brent_stuck import first_stuck, pick_itmax
-from vcf_joint_reference import NONE, PLANTED_TRIO, PLANTED_TRIO_OWN_AF, JointFamilies, make_case, transmission, trio_block
-from vcf_phase_reference import large_nuclear_case, trio_pedigree
+from vcf_joint_reference import NONE, PLANTED_TRIO, PLANTED_TRIO_OWN_AF, JointFamilies, transmission, trio_block
+import vcf_plane_common as common
+from vcf_phase_reference import trio_pedigree
 
 pytestmark = pytest.mark.gpu
 
@@ -47,49 +48,24 @@ POST_ATOL = 3 * 2.0 ** -25 + DOSE_ATOL
 # (k_vcf_joint_nuc's nuclear branch).  The synthetic shapes list the mother first in some families.
 REF_CASES = [("mixed", 31), ("quad", 70), ("single", 12), ("ext10", 3), ("extmix", 5), ("nuclear", 0)]
 
-_DATA = {}
-
-
 def dataset(tmp_path_factory, shape, nfam):
     """(owner of the pedigree, its view, block, refalt, max_batch), generated once per case and left unchanged."""
-    key = (shape, nfam)
-    if key not in _DATA:
-        nsites, batch = (16, 12) if shape == "extmix" else (96, 64)
-        if shape == "nuclear":
-            ped, block, refalt = large_nuclear_case(nsites)
-            _DATA[key] = (ped, ped, block, refalt, batch)
-        else:
-            ped, block, refalt = make_case(str(tmp_path_factory.mktemp(f"vj_{shape}_{nfam}")), shape, nfam, nsites)
-            _DATA[key] = (ped, ped.view, block, refalt, batch)
-    return _DATA[key]
+    nsites, batch = (16, 12) if shape == "extmix" else (96, 64)
+    return common.dataset(tmp_path_factory, "vj", shape, nfam, nsites) + (batch,)
 
 
 def run_batches(eng, block, refalt, batch, entry="run", joint=True, post=False, phase=False):
     """Every batch through one entry point: (results, calls as (best, gq, label) int arrays, (g, lp) or None, posterior
     plane or None, phase plane or None)."""
-    res, calls, g, lp, po, ph = [], [], [], [], [], []
-    zeros = np.zeros(block.shape[:2], np.uint32)
-    for s in range(0, len(refalt), batch):
-        sl = slice(s, s + batch)
-        if entry == "run":
-            r, c = eng.run(block[sl], zeros[sl], refalt[sl])
-        elif entry == "run_vcf":
-            r, c = eng.run_vcf(block[sl], refalt[sl])
-        else:
-            eng.submit(block[sl], zeros[sl], refalt[sl])
-            r, c = eng.collect()
-        res.append(r)
-        calls.append(np.stack([c[f].astype(np.int16) for f in ("best", "gq", "label")], axis=-1))
+    def fetch(c):
+        a = b = None
         if joint:
             a, b = eng.vcf_joint()
             assert a.shape == b.shape == (len(c), eng.n_person) and a.dtype == np.uint8 and b.dtype == np.float32
-            g.append(a)
-            lp.append(b)
-        if post:
-            po.append(eng.vcf_posteriors())
-        if phase:
-            ph.append(eng.vcf_phase())
-    return (np.concatenate(res), np.concatenate(calls), (np.concatenate(g), np.concatenate(lp)) if joint else None,
+        return a, b, eng.vcf_posteriors() if post else None, eng.vcf_phase() if phase else None
+    res, calls, got = common.run_batches(eng, block, refalt, batch, entry, fetch)
+    g, lp, po, ph = ([x[i] for x in got] for i in range(4))
+    return (res, calls, (np.concatenate(g), np.concatenate(lp)) if joint else None,
             np.concatenate(po) if post else None, np.concatenate(ph) if phase else None)
 
 
@@ -373,41 +349,12 @@ def test_planted_trio_of_the_first_example(built):
 
 JG_HEADER = ('##FORMAT=<ID=JG,Number=1,Type=String,Description="Genotype in the Family\'s Most Probable Joint Configuration">')
 JL_HEADER = '##FORMAT=<ID=JL,Number=1,Type=Float,Description="Log10 Posterior Probability of That Configuration">'
-SRC = os.path.join(EXAMPLE, "testvcf.in.vcf.gz")
-
-
-def _cli(tmp_path, name, extra, src=None):
-    out = tmp_path / name
-    r = subprocess.run([pm.BIN_PATH, "-p", "test.ped", "-d", "test.dat", "--in_vcf", src or SRC, "--out_vcf", str(out)] + extra,
-                       cwd=EXAMPLE, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return out.read_text().splitlines()
+SRC, _cli, _same = common.SRC, common.cli, common.same
 
 
 def _strip(lines):
     """The output without the JG and JL header lines and sub-fields."""
-    out = []
-    for l in lines:
-        if l.startswith("##FORMAT=<ID=JG,") or l.startswith("##FORMAT=<ID=JL,"):
-            continue
-        if l.startswith("#"):
-            out.append(l)
-            continue
-        c = l.split("\t")
-        fmt = c[8].split(":")
-        k = fmt.index("JG")
-        assert fmt[k + 1] == "JL" and fmt[k + 2] in ("PL", "GL") and k == len(fmt) - 3, c[8]
-        c[8] = ":".join(fmt[:k] + fmt[k + 2:])
-        for i in range(9, len(c)):
-            v = c[i].split(":")
-            c[i] = ":".join(v[:k] + v[k + 2:])
-        out.append("\t".join(c))
-    return out
-
-
-def _same(a, b):   # (the ##Polymutt= line records the command line)
-    drop = lambda ls: [l for l in ls if not l.startswith("##Polymutt=")]
-    return drop(a) == drop(b)
+    return common.strip_fields(lines, ("JG", "JL"), lambda fmt, k: fmt[k + 2] in ("PL", "GL") and k == len(fmt) - 3)
 
 
 def _example_plane():

@@ -27,7 +27,8 @@ import polymutt_amd as pm
 from conftest import EXAMPLE
 from parity import DOSE_ATOL, _nonfinite_problem
 from test_brent_stuck import first_stuck, pick_itmax
-from vcf_phase_reference import PhaseFamilies, large_nuclear_case, make_case
+import vcf_plane_common as common
+from vcf_phase_reference import PhaseFamilies
 
 pytestmark = pytest.mark.gpu
 
@@ -40,46 +41,26 @@ BATCH, NSITES = 64, 96
 # the five peel schedules; "nuclear": families of three and four children (k_vcf_phase_nuc's nuclear branch)
 REF_CASES = [("mixed", 31), ("quad", 70), ("single", 12), ("ext10", 3), ("extmix", 5), ("nuclear", 0)]
 
-_DATA = {}
+PEEL_CASES = [("ext10", 3, 96, 64), ("extmix", 5, 16, 12)]   # (shape, families, sites, max_batch)
 
 
-def dataset(tmp_path_factory, shape, nfam):
+def dataset(tmp_path_factory, shape, nfam, nsites=NSITES):
     """(owner of the pedigree, its view, block, refalt), generated once per case and left unchanged."""
-    key = (shape, nfam)
-    if key not in _DATA:
-        if shape == "nuclear":
-            ped, block, refalt = large_nuclear_case(NSITES)
-            _DATA[key] = (ped, ped, block, refalt)
-        else:
-            ped, block, refalt = make_case(str(tmp_path_factory.mktemp(f"vph_{shape}_{nfam}")), shape, nfam, NSITES)
-            _DATA[key] = (ped, ped.view, block, refalt)
-    return _DATA[key]
+    return common.dataset(tmp_path_factory, "vph", shape, nfam, nsites)
 
 
-def run_batches(eng, block, refalt, entry="run", phase=True, post=False):
+def run_batches(eng, block, refalt, entry="run", phase=True, post=False, batch=BATCH):
     """Every batch through one entry point: (results, calls as (best, gq, label) int arrays, phase plane or None,
     posterior plane or None)."""
-    res, calls, ph, po = [], [], [], []
-    zeros = np.zeros(block.shape[:2], np.uint32)
-    for s in range(0, len(refalt), BATCH):
-        sl = slice(s, s + BATCH)
-        if entry == "run":
-            r, c = eng.run(block[sl], zeros[sl], refalt[sl])
-        elif entry == "run_vcf":
-            r, c = eng.run_vcf(block[sl], refalt[sl])
-        else:
-            eng.submit(block[sl], zeros[sl], refalt[sl])
-            r, c = eng.collect()
-        res.append(r)
-        calls.append(np.stack([c[f].astype(np.int16) for f in ("best", "gq", "label")], axis=-1))
+    def fetch(c):
+        p = None
         if phase:
             p = eng.vcf_phase()
             assert p.shape == (len(c), eng.n_person, 2) and p.dtype == np.float32
-            ph.append(p)
-        if post:
-            po.append(eng.vcf_posteriors())
-    return (np.concatenate(res), np.concatenate(calls), np.concatenate(ph) if phase else None,
-            np.concatenate(po) if post else None)
+        return p, eng.vcf_posteriors() if post else None
+    res, calls, got = common.run_batches(eng, block, refalt, batch, entry, fetch)
+    return (res, calls, np.concatenate([g[0] for g in got]) if phase else None,
+            np.concatenate([g[1] for g in got]) if post else None)
 
 
 def check_plane(ph, founders, label):
@@ -238,6 +219,24 @@ def test_schedule_compiler_on_and_off(built, tmp_path_factory, monkeypatch):
     assert planes[0].tobytes() == planes[1].tobytes() and (planes[0] != 0).any()
 
 
+@pytest.mark.parametrize("shape,nfam,nsites,batch", PEEL_CASES)
+def test_peel_workspace_in_lds_and_in_hbm(built, tmp_path_factory, monkeypatch, shape, nfam, nsites, batch):
+    """k_vcf_phase_es<true> and k_vcf_phase_es<false> (PM_ES_POST_HBM) write the same plane: the two workspaces hold the
+    same doubles in the same order.  Site results and genotype rows are the same bytes too."""
+    ped, view, block, refalt = dataset(tmp_path_factory, shape, nfam, nsites)
+    outs = []
+    for hbm in (False, True):
+        if hbm:
+            monkeypatch.setenv("PM_ES_POST_HBM", "1")   # (read when the engine is created)
+        eng = pm.Engine(view, pm.Params.defaults(vcf_mode=1), max_batch=batch)
+        eng.set_vcf_phase(True)
+        outs.append(run_batches(eng, block, refalt, batch=batch))
+        eng.close()
+    (r0, c0, p0, _), (r1, c1, p1, _) = outs
+    assert p0.tobytes() == p1.tobytes() and (p0 != 0).any()
+    assert r0.tobytes() == r1.tobytes() and c0.tobytes() == c1.tobytes()
+
+
 def test_stuck_site_keeps_the_returned_rows(built, tmp_path_factory, monkeypatch):
     ped, view, block, refalt = dataset(tmp_path_factory, "mixed", 31)
     par = pm.Params.defaults(vcf_mode=1)
@@ -270,41 +269,12 @@ PQ_HEADER = ('##FORMAT=<ID=PQ,Number=1,Type=Integer,Description="Phred-scaled qu
              '(paternal|maternal)">')
 
 
-def _cli(tmp_path, name, extra, src=None):
-    out = tmp_path / name
-    r = subprocess.run([pm.BIN_PATH, "-p", "test.ped", "-d", "test.dat", "--in_vcf", src or os.path.join(EXAMPLE, "testvcf.in.vcf.gz"),
-                        "--out_vcf", str(out)] + extra, cwd=EXAMPLE, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return out.read_text().splitlines()
+_cli, _same = common.cli, common.same
 
 
 def _strip(lines):
     """The output without the PQ header line and sub-field and with every phased GT unphased again."""
-    out = []
-    for l in lines:
-        if l.startswith("##FORMAT=<ID=PQ,"):
-            continue
-        if l.startswith("#"):
-            out.append(l)
-            continue
-        c = l.split("\t")
-        fmt = c[8].split(":")
-        k = fmt.index("PQ")
-        assert fmt[k + 1] in ("PL", "GL") and k == len(fmt) - 2, c[8]
-        c[8] = ":".join(fmt[:k] + fmt[k + 1:])
-        for i in range(9, len(c)):
-            v = c[i].split(":")
-            if "|" in v[0]:
-                assert v[0] in ("0|1", "1|0"), v[0]
-                v[0] = "0/1"
-            c[i] = ":".join(v[:k] + v[k + 1:])
-        out.append("\t".join(c))
-    return out
-
-
-def _same(a, b):   # (the ##Polymutt= line records the command line)
-    drop = lambda ls: [l for l in ls if not l.startswith("##Polymutt=")]
-    return drop(a) == drop(b)
+    return common.strip_fields(lines, ("PQ",), lambda fmt, k: fmt[k + 1] in ("PL", "GL") and k == len(fmt) - 2, unphase=True)
 
 
 def _founder_columns(lines):

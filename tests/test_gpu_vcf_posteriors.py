@@ -28,7 +28,8 @@ from conftest import EXAMPLE
 from oracle_binding import Oracle
 from parity import DOSE_ATOL, _nonfinite_problem
 from test_brent_stuck import first_stuck, pick_itmax
-from vcf_posterior_reference import Families, make_case, three
+import vcf_plane_common as common
+from vcf_posterior_reference import Families, three
 
 pytestmark = pytest.mark.gpu
 
@@ -45,37 +46,23 @@ GP_CASES = [("mixed", 31), ("quad", 70), ("single", 12), ("ext10", 3), ("extmix"
 # test_engine_vcf_mode_matches_oracle's shapes plus a lone peeled family
 DS_CASES = [("quad", 40), ("mixed", 31), ("single", 12), ("ext10", 8), ("roof", 8), ("quad", 1), ("ext10", 1)]
 
-_DATA = {}
+PEEL_CASES = [("ext10", 3, 96, 64), ("extmix", 5, 16, 12)]   # (shape, families, sites, max_batch)
 
 
-def dataset(tmp_path_factory, shape, nfam):
+def dataset(tmp_path_factory, shape, nfam, nsites=NSITES):
     """(ped, block, refalt), generated once per case and left unchanged."""
-    key = (shape, nfam)
-    if key not in _DATA:
-        _DATA[key] = make_case(str(tmp_path_factory.mktemp(f"vp_{shape}_{nfam}")), shape, nfam, NSITES)
-    return _DATA[key]
+    ped, _, block, refalt = common.dataset(tmp_path_factory, "vp", shape, nfam, nsites)
+    return ped, block, refalt
 
 
-def run_batches(eng, block, refalt, entry="run", posteriors=True):
+def run_batches(eng, block, refalt, entry="run", posteriors=True, batch=BATCH):
     """Every batch through one entry point: (results, calls as (best, gq, label) int arrays, plane or None)."""
-    res, calls, post = [], [], []
-    zeros = np.zeros(block.shape[:2], np.uint32)
-    for s in range(0, len(refalt), BATCH):
-        sl = slice(s, s + BATCH)
-        if entry == "run":
-            r, c = eng.run(block[sl], zeros[sl], refalt[sl])
-        elif entry == "run_vcf":
-            r, c = eng.run_vcf(block[sl], refalt[sl])
-        else:
-            eng.submit(block[sl], zeros[sl], refalt[sl])
-            r, c = eng.collect()
-        res.append(r)
-        calls.append(np.stack([c[f].astype(np.int16) for f in ("best", "gq", "label")], axis=-1))
-        if posteriors:
-            p = eng.vcf_posteriors()
-            assert p.shape == (len(c), eng.n_person, 3) and p.dtype == np.float32
-            post.append(p)
-    return np.concatenate(res), np.concatenate(calls), (np.concatenate(post) if posteriors else None)
+    def fetch(c):
+        p = eng.vcf_posteriors()
+        assert p.shape == (len(c), eng.n_person, 3) and p.dtype == np.float32
+        return p
+    res, calls, post = common.run_batches(eng, block, refalt, batch, entry, fetch if posteriors else lambda c: None)
+    return res, calls, (np.concatenate(post) if posteriors else None)
 
 
 def check_plane(post, calls, label):
@@ -276,6 +263,24 @@ def test_schedule_compiler_on_and_off(built, tmp_path_factory, monkeypatch):
     assert planes[0].tobytes() == planes[1].tobytes() and (planes[0] != 0).any()
 
 
+@pytest.mark.parametrize("shape,nfam,nsites,batch", PEEL_CASES)
+def test_peel_workspace_in_lds_and_in_hbm(built, tmp_path_factory, monkeypatch, shape, nfam, nsites, batch):
+    """k_vcf_post_es<true> and k_vcf_post_es<false> (PM_ES_POST_HBM) write the same plane: the two workspaces hold the same
+    doubles in the same order.  Site results and genotype rows are the same bytes too."""
+    ped, block, refalt = dataset(tmp_path_factory, shape, nfam, nsites)
+    outs = []
+    for hbm in (False, True):
+        if hbm:
+            monkeypatch.setenv("PM_ES_POST_HBM", "1")   # (read when the engine is created)
+        eng = pm.Engine(ped.view, pm.Params.defaults(vcf_mode=1), max_batch=batch)
+        eng.set_vcf_posteriors(True)
+        outs.append(run_batches(eng, block, refalt, batch=batch))
+        eng.close()
+    (r0, c0, p0), (r1, c1, p1) = outs
+    assert p0.tobytes() == p1.tobytes() and (p0 != 0).any()
+    assert r0.tobytes() == r1.tobytes() and c0.tobytes() == c1.tobytes()
+
+
 def test_stuck_site_keeps_the_returned_rows(built, tmp_path_factory, monkeypatch):
     ped, block, refalt = dataset(tmp_path_factory, "mixed", 31)
     par = pm.Params.defaults(vcf_mode=1)
@@ -302,32 +307,12 @@ def test_stuck_site_keeps_the_returned_rows(built, tmp_path_factory, monkeypatch
     eng.close()
 
 
-def _cli(tmp_path, name, extra):
-    out = tmp_path / name
-    r = subprocess.run([pm.BIN_PATH, "-p", "test.ped", "-d", "test.dat", "--in_vcf", os.path.join(EXAMPLE, "testvcf.in.vcf.gz"),
-                        "--out_vcf", str(out)] + extra, cwd=EXAMPLE, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return out.read_text().splitlines()
+_cli = common.cli
 
 
 def _strip(lines):
     """The output without the two header lines and without the DS and GP sub-fields."""
-    out = []
-    for l in lines:
-        if l.startswith("##FORMAT=<ID=DS,") or l.startswith("##FORMAT=<ID=GP,"):
-            continue
-        if l.startswith("#"):
-            out.append(l)
-            continue
-        c = l.split("\t")
-        fmt = c[8].split(":")
-        assert fmt[3:5] == ["DS", "GP"], c[8]
-        c[8] = ":".join(fmt[:3] + fmt[5:])
-        for i in range(9, len(c)):
-            v = c[i].split(":")
-            c[i] = ":".join(v[:3] + v[5:])
-        out.append("\t".join(c))
-    return out
+    return common.strip_fields(lines, ("DS", "GP"), lambda fmt, k: k == 3)
 
 
 def test_cli_prints_ds_and_gp(built, tmp_path):
