@@ -558,6 +558,43 @@ int pm_engine_set_vcf_joint(pm_engine *eng, int32_t on);
  * batch returned.  PM_EINVAL: the feature is off, or a submitted batch has not been collected. */
 int pm_engine_vcf_joint(pm_engine *eng, int32_t *n_rows, pm_vcf_joint *out);
 
+/* The pedigree check of a vcf_mode engine (pm_engine_set_vcf_pedcheck / pm_engine_vcf_pedcheck; additive to ABI 8: callers
+ * detect the feature by these symbols; the reference has no counterpart).  Unlike the planes it is one value per person
+ * summed over every written row of every autosomal batch.  For a non-founder c (both parents stated inside its family) and
+ * a row with the frequency f (pm_site_result.af; 1 - theta on a monomorphic row),
+ *   L0      = the family's likelihood under the stated pedigree: the founder priors, the single-family prior mode, the plain
+ *             transmission T and the family routing of the genotype rows and the three planes;
+ *   L_fa    = the same with only c's transmission replaced by T_fa[a][b][k] = Sum_a' pi(a') T[a'][b][k], the paternal
+ *             allele drawn from the population: pi = (f^2, 2 f (1 - f), (1 - f)^2);
+ *   L_mo    = its mirror;   L_both = the same with T_un[a][b][k] = pi(k).
+ * Everybody else, c's own children included, keeps its table.  A row counts for c when all four are finite and positive;
+ * it then adds 1 to n and llrint(log10(L0 / L_h) * 2^28) to q[h], h = father, mother, both.  The sums are int64, so they
+ * do not depend on how the rows were split into batches, on the launch shape or on the order of the additions: value =
+ * q * 2^-28 log10 units, a row's quantisation error at most 2^-29.  A positive sum supports the stated link.  chrX / chrY
+ * / MT sections add nothing, and neither do the children of a family of more than 255 persons (the kernels' work lists pack
+ * a member's index into 8 bits, as the phase plane's do): they are listed with n = 0. */
+typedef struct {
+  int32_t person, pad;         /* pm_pedigree index of the non-founder; pad is written as 0 */
+  int64_t n;                   /* rows counted */
+  int64_t q[3];                /* father, mother, both: Sum llrint(log10(L0 / L_h) * 2^28) */
+} pm_vcf_pedcheck;
+
+/* Switch the pedigree check on or off (off at creation).  on: the sums are allocated and zeroed; with it on every
+ * autosomal batch runs one extra pass after the joint plane's (k_vcf_pedcheck_lean / k_vcf_pedcheck_nuc /
+ * k_vcf_pedcheck_es, routed as the planes' kernels are) that adds to the sums and writes nothing else: every other output
+ * of the engine is that of the engine without it, byte for byte.  on while on keeps the sums.  off frees them; off =
+ * nothing allocated, nothing launched.  A failed on frees what it allocated.  PM_EINVAL: an engine without vcf_mode, or a
+ * submitted batch not yet collected. */
+int pm_engine_set_vcf_pedcheck(pm_engine *eng, int32_t on);
+
+/* Zero the sums.  PM_EINVAL as above, or with the feature off. */
+int pm_engine_reset_vcf_pedcheck(pm_engine *eng);
+
+/* *n_kids = the pedigree's non-founders; out[i], by ascending person index, holds the sums over every batch finished
+ * since on / reset.  out may be NULL (the count alone).  PM_EINVAL: the feature is off, or a submitted batch has not been
+ * collected. */
+int pm_engine_vcf_pedcheck(pm_engine *eng, int32_t *n_kids, pm_vcf_pedcheck *out);
+
 /* Page-locked host memory for pm_engine_submit's inputs and the result rows (H2D/D2H at full PCIe rate). */
 int pm_host_alloc(uint64_t bytes, void **h_ptr);
 int pm_host_free(void *h_ptr);

@@ -10,6 +10,7 @@
 #include "vcf_post_dev.h"
 #include "vcf_phase_dev.h"
 #include "vcf_joint_dev.h"
+#include "vcf_pedcheck_dev.h"
 
 #define PM_BRENT_X(part, ...) extern template __global__ void k_brent<__VA_ARGS__>(DevArgs, int);
 PM_BRENT_VARIANTS
@@ -40,8 +41,11 @@ struct Plane {
 struct PlanList {
   std::vector<int> h[2];
   int* d[2] = {nullptr, nullptr};
+  int users = 0;   // the features that hold the device copy (acquire / release)
   int upload();
   void free();
+  int acquire() { if (users == 0) { if (int rc = upload()) { free(); return rc; } } users++; return 0; }
+  void release() { if (users > 0 && --users == 0) free(); }
 };
 
 struct pm_engine {
@@ -182,6 +186,13 @@ struct pm_engine {
   PlanList vj_fams;                         // the peeled families
   double* d_vj_ws = nullptr;                // k_vcf_joint_es<false>'s workspace (only where the LDS one does not fit)
   int vj_ws_per_lane = 0, vj_grid = 0;      // doubles per thread; HBM grid
+  // the pedigree check (pm_engine_set_vcf_pedcheck): sums over every autosomal batch; off = no buffer, no launch
+  bool pc_on = false;
+  std::vector<int> pc_person;               // the non-founders by ascending person index
+  unsigned long long* d_pc_acc = nullptr;   // [non-founders][4]: n, q father, q mother, q both
+  int* d_pc_slot = nullptr;                 // [n_person] index into pc_person, -1 for a founder
+  bool vph_holds_kids = false, pc_holds_kids = false;               // the phase plane / the check holds vph_kids' device copy
+  PlanList pc_nuc_kids;                     // the children of the nuclear families plan 0 does not peel
   std::vector<int> fam_kind_h, fam_perm_h;
   std::vector<int32_t> fa_h, mo_h;  // family-local parent indices (-1: none)
   unsigned long long* d_counters = nullptr;
@@ -239,6 +250,7 @@ int PlanList::upload() {
 }
 void PlanList::free() {
   for (int plan = 0; plan < 2; plan++) dfree((void**)&d[plan]);
+  users = 0;
 }
 // a persistent grid rounded down to whole rounds of the 8 XCDs (the kernels' XCD-aware item order needs gridDim % 8 == 0;
 // they fall back to plain order otherwise), never below one block
@@ -419,10 +431,11 @@ void pm_engine_destroy(pm_engine* E) {
                   E->d_pdn_top, E->d_pdn_all, E->d_pdn_line, E->d_pdn_kids, E->d_pdn_is_kid, E->d_pdn_jbuf,
                   E->d_vdn_terms, E->d_vdn_co, E->d_vdn_ws, E->d_vdnx_terms, E->d_vdnx_ws, E->d_vw_row_site, E->d_vw_pfam, E->d_vw_fam_top, E->d_vw_fam_sum,
                   E->d_vw_fam_all, E->d_vw_fam_line, E->d_vw_car_top, E->d_vw_car_all, E->d_vw_car_line, E->d_vw_kids, E->d_vw_is_kid,
-                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf, E->vp.d, E->vph.d, E->vj.d, E->d_vj_ws};
+                  E->d_vw_jbuf, E->d_vwx_kids, E->d_vwx_is_kid, E->d_vwx_jbuf, E->vp.d, E->vph.d, E->vj.d, E->d_vj_ws, E->d_pc_acc, E->d_pc_slot};
   for (void* b : bufs) if (b) hipFree(b);
   E->vph_kids.free();
   E->vj_fams.free();
+  E->pc_nuc_kids.free();
   for (auto& pl : E->d_jit_slots)
     for (int* b : pl) if (b) hipFree(b);
   for (auto& pl : E->d_fused_tab)
@@ -1316,6 +1329,35 @@ static int launch_vcf_joint(pm_engine* E, const DevArgs& A, bool lean, bool es) 
                            k_vcf_joint_es<false>, es_block_shape(E, E->vj_ws_per_lane), E->vj_grid);
 }
 
+// The pedigree check's pass (vcf_pedcheck_dev.h) over an autosomal batch's rows, routed as the planes' passes are.  Every
+// kernel's threads own a family or child over a stripe of rows: blocks enough for eight rows per thread when every site of
+// the batch is written, within the stage's grid (the peel's HBM workspace holds that many blocks' lanes).
+static int launch_vcf_pedcheck(pm_engine* E, const DevArgs& A, int n, bool lean, bool es) {
+  const int plan = E->use_plan1 ? 1 : 0;
+  VpcArgs P;
+  P.acc = E->d_pc_acc; P.slot = E->d_pc_slot; P.kids = nullptr; P.n_kids = 0;
+  auto grid_for = [&](int items, int bt, int cap) {
+    const int row_lanes = std::max(1, bt / std::max(1, std::min(items, bt)));
+    return std::max(1, std::min(cap, (n + row_lanes * 8 - 1) / (row_lanes * 8)));
+  };
+  if (lean) {
+    hipLaunchKernelGGL(k_vcf_pedcheck_lean, dim3(grid_for(E->n_fam, 256, E->grid_post)), dim3(256), 0, E->stream, A, P);
+    HIP_TRY(hipGetLastError());
+  } else if (!E->pc_nuc_kids.h[plan].empty()) {
+    P.kids = E->pc_nuc_kids.d[plan]; P.n_kids = (int)E->pc_nuc_kids.h[plan].size();
+    hipLaunchKernelGGL(k_vcf_pedcheck_nuc, dim3(grid_for(P.n_kids, 256, E->grid_post)), dim3(256), 0, E->stream, A, P);
+    HIP_TRY(hipGetLastError());
+  }
+  if (es && !E->vph_kids.h[plan].empty()) {
+    P.kids = E->vph_kids.d[plan]; P.n_kids = (int)E->vph_kids.h[plan].size();
+    const EsShape sh = es_block_shape(E, E->ws_per_lane + 4);   // (+ 4: the block's sums behind the workspace)
+    if (sh.bt) hipLaunchKernelGGL(k_vcf_pedcheck_es<true>, dim3(grid_for(P.n_kids, sh.bt, sh.grid)), dim3(sh.bt), sh.lds_bytes, E->stream, A, P);
+    else hipLaunchKernelGGL(k_vcf_pedcheck_es<false>, dim3(grid_for(P.n_kids, 256, E->grid_post)), dim3(256), 0, E->stream, A, P);
+    HIP_TRY(hipGetLastError());
+  }
+  return PM_OK;
+}
+
 static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* dm, const uint8_t* ref, pm_site_result* res,
                         pm_geno_call* calls) {
   DevArgs A = make_args(E, n, pl, dm, ref, res, calls);
@@ -1426,6 +1468,10 @@ static int run_pipeline(pm_engine* E, int n, const uint8_t* pl, const uint32_t* 
     if (E->vj.on) {
       HIP_TRY(hipGetLastError());
       if ((rc = launch_vcf_joint(E, A, lean, es))) return rc;
+    }
+    if (E->pc_on && E->chrom == PM_CHR_AUTO) {
+      HIP_TRY(hipGetLastError());
+      if ((rc = launch_vcf_pedcheck(E, A, n, lean, es))) return rc;
     }
   }
   HIP_TRY(hipGetLastError());
@@ -1677,7 +1723,8 @@ int pm_engine_vcf_posteriors(pm_engine* E, int32_t* n_rows, pm_vcf_post* out) {
 
 static void vph_off(pm_engine* E) {
   plane_free(E->vph);
-  E->vph_kids.free();
+  if (E->vph_holds_kids) E->vph_kids.release();
+  E->vph_holds_kids = false;
 }
 
 int pm_engine_set_vcf_phase(pm_engine* E, int32_t on) {
@@ -1685,7 +1732,7 @@ int pm_engine_set_vcf_phase(pm_engine* E, int32_t on) {
   if (!on) { vph_off(E); return PM_OK; }
   if (E->vph.on) return PM_OK;   // (already on: the last batch's plane stays)
   int rc = plane_alloc_clear(E, E->vph);   // (cleared: the founders of peeled families are never written)
-  if (!rc) rc = E->vph_kids.upload();
+  if (!rc && !(rc = E->vph_kids.acquire())) E->vph_holds_kids = true;
   if (rc) vph_off(E);
   return rc;
 }
@@ -1731,6 +1778,73 @@ int pm_engine_set_vcf_joint(pm_engine* E, int32_t on) {
 
 int pm_engine_vcf_joint(pm_engine* E, int32_t* n_rows, pm_vcf_joint* out) {
   return plane_fetch(E, &pm_engine::vj, "vcf_joint", n_rows, out);
+}
+
+static void pc_off(pm_engine* E) {
+  E->pc_on = false;
+  dfree((void**)&E->d_pc_acc);
+  dfree((void**)&E->d_pc_slot);
+  if (E->pc_holds_kids) E->vph_kids.release();
+  E->pc_holds_kids = false;
+  E->pc_nuc_kids.free();
+}
+
+int pm_engine_set_vcf_pedcheck(pm_engine* E, int32_t on) {
+  if (int rc = plane_guard(E, "vcf_pedcheck")) return rc;
+  if (!on) { pc_off(E); return PM_OK; }
+  if (E->pc_on) return PM_OK;   // (already on: the sums stay)
+  // the non-founders: both parents stated inside the family
+  std::vector<int> slot(E->n_person, -1);
+  E->pc_person.clear();
+  for (int plan = 0; plan < 2; plan++) E->pc_nuc_kids.h[plan].clear();
+  for (int f = 0; f < E->n_fam; f++) {
+    const int p0 = E->fam_start_h[f], n = E->fam_start_h[f + 1] - p0;
+    if (E->fam_kind_h[f] == PM_FAM_FOUNDERS) continue;
+    for (int j = 0; j < n; j++) {
+      const int fa = E->fa_h[p0 + j], mo = E->mo_h[p0 + j];
+      if (fa < 0 || mo < 0 || fa >= n || mo >= n || fa == mo) continue;
+      slot[p0 + j] = (int)E->pc_person.size();
+      E->pc_person.push_back(p0 + j);
+      // (family << 8 | member, as vph_kids packs its entries: the children of a family of more than 255 persons are on no
+      // list, here as there, and keep n = 0 unless the section runs the lean loop)
+      if (E->fam_kind_h[f] == PM_FAM_NUCLEAR && n <= 255 && j >= 2) E->pc_nuc_kids.h[0].push_back(f << 8 | j);
+    }
+  }
+  const size_t cells = std::max<size_t>(1, E->pc_person.size() * 4);
+  int rc = dalloc(&E->d_pc_acc, cells);
+  if (!rc) rc = dalloc(&E->d_pc_slot, (size_t)E->n_person);
+  if (!rc && !(rc = E->vph_kids.acquire())) E->pc_holds_kids = true;   // (the phase plane's list, one device copy for both)
+  if (!rc) rc = E->pc_nuc_kids.upload();
+  if (!rc && hipMemset(E->d_pc_acc, 0, cells * sizeof(unsigned long long)) != hipSuccess) rc = PM_EHIP;
+  if (!rc && hipMemcpy(E->d_pc_slot, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice) != hipSuccess) rc = PM_EHIP;
+  if (rc) { pc_off(E); return rc; }
+  E->pc_on = true;
+  return PM_OK;
+}
+
+int pm_engine_reset_vcf_pedcheck(pm_engine* E) {
+  if (int rc = plane_guard(E, "vcf_pedcheck")) return rc;
+  if (!E->pc_on) return plane_refuse("pm_engine_reset_", "vcf_pedcheck", "the feature is off (pm_engine_set_vcf_pedcheck)");
+  HIP_TRY(hipMemset(E->d_pc_acc, 0, std::max<size_t>(1, E->pc_person.size() * 4) * sizeof(unsigned long long)));
+  return PM_OK;
+}
+
+int pm_engine_vcf_pedcheck(pm_engine* E, int32_t* n_kids, pm_vcf_pedcheck* out) {
+  if (!E || !n_kids) return plane_refuse("pm_engine_", "vcf_pedcheck", "invalid arguments");
+  if (!E->pc_on) return plane_refuse("pm_engine_", "vcf_pedcheck", "the feature is off (pm_engine_set_vcf_pedcheck)");
+  if (E->pending_n >= 0) return plane_refuse("pm_engine_", "vcf_pedcheck", "a submitted batch has not been collected");
+  *n_kids = (int32_t)E->pc_person.size();
+  if (out && *n_kids > 0) {
+    std::vector<long long> acc((size_t)*n_kids * 4);
+    HIP_TRY(hipSetDevice(E->device));
+    HIP_TRY(hipStreamSynchronize(E->stream));
+    HIP_TRY(hipMemcpy(acc.data(), E->d_pc_acc, sizeof(long long) * acc.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < *n_kids; i++) {
+      out[i].person = E->pc_person[i]; out[i].pad = 0; out[i].n = acc[4 * (size_t)i];
+      for (int h = 0; h < 3; h++) out[i].q[h] = acc[4 * (size_t)i + 1 + h];
+    }
+  }
+  return PM_OK;
 }
 
 int pm_engine_set_vcf_denovo_chrx(pm_engine* E, int32_t on) {

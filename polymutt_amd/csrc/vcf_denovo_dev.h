@@ -46,10 +46,13 @@ __device__ __forceinline__ int vdn_pick3(const int* g, int s) { return s == 0 ? 
 // CL: three more persons c0, c1, c2 (family-local indices) are clamped to the state sets m0, m1, m2 (bit s = state s of
 // (g11, g12, g22) allowed), where the initial partials are filled, as d_es_lk<10, true> does (k_vdn_who, k_vdn_who_x);
 // without CL nothing is added.
-template <bool CL = false, bool X = false>
+// ALT (vcf_pedcheck_dev.h): the steps whose child is the family-local person alt.c -- type 1 from it, type 3 to it -- take
+// alt's table in place of tdn / tpl; without ALT nothing is added.
+struct EsAltNone {};
+template <bool CL = false, bool X = false, bool ALT = false, class Alt = EsAltNone>
 __device__ __forceinline__ double d_es_lk3_vdn(const DevArgs& A, int f, const uint8_t* pl, const double* lk, const int* gidx, double freq,
                                                const double* tdn, const double* tpl, double* ws, size_t st, int c0 = -1, int m0 = 0,
-                                               int c1 = -1, int m1 = 0, int c2 = -1, int m2 = 0) {
+                                               int c1 = -1, int m1 = 0, int c2 = -1, int m2 = 0, Alt alt = Alt()) {
   const int p0 = A.fam_start[f], n = A.fam_start[f + 1] - p0, nf = A.fam_founders[f];
 #define PP(i, j) ws[((size_t)(i) * 3 + (j)) * st]
 #define MPP(sl, x, y) ws[((size_t)n * 3 + (size_t)(sl) * 9 + (x) * 3 + (y)) * st]
@@ -82,6 +85,21 @@ __device__ __forceinline__ double d_es_lk3_vdn(const DevArgs& A, int f, const ui
       double pk[3];
 #pragma unroll
       for (int k = 0; k < 3; k++) pk[k] = PP(from0, k);
+      if constexpr (ALT) {
+        if (alt.is_child(from0)) {
+          const bool first_fa = alt.is_father(to0);   // the partial's first index is the father's state
+#pragma unroll
+          for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+              double sum = 0;
+#pragma unroll
+              for (int k = 0; k < 3; k++) sum += alt.t(first_fa, i, j, k) * pk[k];
+              MPP(slot, i, j) *= sum;
+            }
+          continue;
+        }
+      }
       for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) {
           double sum = 0;
@@ -105,6 +123,22 @@ __device__ __forceinline__ double d_es_lk3_vdn(const DevArgs& A, int f, const ui
       double pf[3], pm[3], sum[3];
 #pragma unroll
       for (int k = 0; k < 3; k++) { pf[k] = PP(from0, k); pm[k] = PP(from1, k); sum[k] = 0.0; }
+      if constexpr (ALT) {
+        if (alt.is_child(to0)) {
+          const bool first_fa = alt.is_father(from0);
+#pragma unroll
+          for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+              const double w = (slot == 255) ? pf[i] * pm[j] : pf[i] * MPP(slot, i, j) * pm[j];
+#pragma unroll
+              for (int k = 0; k < 3; k++) sum[k] += w * alt.t(first_fa, i, j, k);
+            }
+#pragma unroll
+          for (int k = 0; k < 3; k++) PP(to0, k) *= sum[k];
+          continue;
+        }
+      }
       for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) {
           const double w = (slot == 255) ? pf[i] * pm[j] : pf[i] * MPP(slot, i, j) * pm[j];

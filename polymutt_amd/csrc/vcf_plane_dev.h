@@ -88,6 +88,43 @@ __device__ __forceinline__ void nuc_family_rows(const DevArgs& A, Founders found
   }
 }
 
+// A reduction over rows (vcf_pedcheck_dev.h) turns the loops above inside out: a work item -- a family, or a child of one --
+// is owned by a thread over a stripe of rows, and the thread keeps the item's NA integer accumulators in registers.  With
+// IT = min(n_items, block) items side by side, thread t takes item base + t % IT on row lane t / IT of block / IT: adjacent
+// lanes hold adjacent items at the same row, so the PL reads stay coalesced, and block b's row lane rl takes the rows
+// b * RL + rl, + grid * RL, ...  body(item, row0, row_step, acc) runs the thread's rows and adds to acc[NA].  The block then
+// sums its row lanes' accumulators in s_acc [block * NA] (LDS integer adds: any order gives the same bits) and hands every
+// non-zero sum to flush(item, a, sum) once: at most one global atomic per (block, accumulator) and launch.  Blocks without
+// a row leave at once.
+template <int NA, class Body, class Flush>
+__device__ __forceinline__ void stripe_items(int rows, int n_items, unsigned long long* s_acc, Body body, Flush flush) {
+  const int bt = blockDim.x;
+  const int IT = n_items < bt ? n_items : bt;
+  if (IT <= 0) return;
+  const int RL = bt / IT;
+  if ((long long)blockIdx.x * RL >= rows) return;
+  const int il = threadIdx.x % IT, rl = threadIdx.x / IT;
+  for (int base = 0; base < n_items; base += IT) {
+    for (int i = threadIdx.x; i < IT * NA; i += bt) s_acc[i] = 0;
+    __syncthreads();
+    if (base + il < n_items && rl < RL) {
+      long long acc[NA];
+#pragma unroll
+      for (int a = 0; a < NA; a++) acc[a] = 0;
+      body(base + il, (int)blockIdx.x * RL + rl, (int)gridDim.x * RL, acc);
+#pragma unroll
+      for (int a = 0; a < NA; a++)
+        if (acc[a]) atomicAdd(&s_acc[il * NA + a], (unsigned long long)acc[a]);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < IT * NA; i += bt) {
+      const unsigned long long v = s_acc[i];
+      if (v && base + i / NA < n_items) flush(base + i / NA, i % NA, v);
+    }
+    __syncthreads();
+  }
+}
+
 // One thread per (row, item of items[n_items]): body(r, item, wsl, stride) with the thread's peel workspace wsl, strided
 // by stride.  LDSWS: the workspace in dynamic LDS, interleaved across the block's threads, instead of the lane-interleaved
 // HBM one (hbm_ws, sized for the grid; DevArgs::ws is idle once the standard stage's kernels are done on the stream).

@@ -4,6 +4,7 @@ Mirrors the reference's per-site call surface (FamilyLikelihoodSeq / NucFamGenot
 SURVEY.md section 8(b)) at batch granularity: ``Engine.run`` evaluates a batch of sites the way one
 iteration of src/main.cpp:327-589 evaluates one site.
 """
+import collections
 import ctypes as C
 import os
 
@@ -109,6 +110,9 @@ VCF_PHASE_DTYPE = np.dtype([("p12", "<f4"), ("p21", "<f4")])   # pm_vcf_phase
 assert VCF_PHASE_DTYPE.itemsize == 8
 VCF_JOINT_DTYPE = np.dtype([("lp", "<f4"), ("g", "u1"), ("pad", "u1", (3,))])   # pm_vcf_joint
 assert VCF_JOINT_DTYPE.itemsize == 8
+VCF_PEDCHECK_DTYPE = np.dtype([("person", "<i4"), ("pad", "<i4"), ("n", "<i8"), ("q", "<i8", (3,))])   # pm_vcf_pedcheck
+assert VCF_PEDCHECK_DTYPE.itemsize == 40
+PedCheck = collections.namedtuple("PedCheck", "person n q llr")   # Engine.vcf_pedcheck()
 
 _lib = None
 
@@ -145,6 +149,9 @@ EXPORTS = {
     "pm_engine_vcf_phase": (i32, [C.c_void_p, P(i32), C.c_void_p]),
     "pm_engine_set_vcf_joint": (i32, [C.c_void_p, i32]),
     "pm_engine_vcf_joint": (i32, [C.c_void_p, P(i32), C.c_void_p]),
+    "pm_engine_set_vcf_pedcheck": (i32, [C.c_void_p, i32]),
+    "pm_engine_reset_vcf_pedcheck": (i32, [C.c_void_p]),
+    "pm_engine_vcf_pedcheck": (i32, [C.c_void_p, P(i32), C.c_void_p]),
     "pm_host_alloc": (i32, [u64, P(C.c_void_p)]),
     "pm_host_free": (i32, [C.c_void_p]),
     "pm_engine_to_planar": (i32, [C.c_void_p, i32, C.c_void_p, C.c_void_p]),
@@ -549,6 +556,29 @@ class Engine:
         jt = np.zeros((n.value, self.n_person), dtype=VCF_JOINT_DTYPE)
         self._check(self.lib.pm_engine_vcf_joint(self.h, C.byref(n), _ptr(jt)))
         return jt["g"].copy(), jt["lp"].copy()
+
+    def set_vcf_pedcheck(self, on=True):
+        """pm_engine_set_vcf_pedcheck (vcf_mode engines): every autosomal batch also adds, for every non-founder, the
+        log10 likelihood ratio of each stated parent link against an unrelated one to sums that live across batches; on
+        allocates and zeroes them, off (the default) frees them and launches nothing.  Every other output is the same
+        bytes either way."""
+        self._check(self.lib.pm_engine_set_vcf_pedcheck(self.h, 1 if on else 0))
+
+    def reset_vcf_pedcheck(self):
+        """pm_engine_reset_vcf_pedcheck: zero the sums."""
+        self._check(self.lib.pm_engine_reset_vcf_pedcheck(self.h))
+
+    def vcf_pedcheck(self):
+        """pm_engine_vcf_pedcheck: PedCheck(person int32 [k], n int64 [k], q int64 [k, 3], llr float64 [k, 3]) for the k
+        non-founders by ascending person index, over every batch finished since on / reset -- the rows counted, the int64
+        sums for (father, mother, both) and llr = q * 2**-28 in log10 units; positive supports the stated link."""
+        k = i32(0)
+        self._check(self.lib.pm_engine_vcf_pedcheck(self.h, C.byref(k), None))
+        pc = np.zeros(k.value, dtype=VCF_PEDCHECK_DTYPE)
+        if k.value:
+            self._check(self.lib.pm_engine_vcf_pedcheck(self.h, C.byref(k), _ptr(pc)))
+        q = pc["q"].copy().reshape(k.value, 3)
+        return PedCheck(pc["person"].copy(), pc["n"].copy(), q, np.ldexp(q.astype(np.float64), -28))
 
     def stuck_site(self):
         """pm_engine_stuck_site: the first site of the last finished batch whose Brent hit ITMAX (-1: none)."""

@@ -53,6 +53,7 @@ Options parse_command_line(int argc, char** argv) {
       {"vcf_denovo_carriers", 'i', &o.vcf_denovo_carriers}, {"vcf_denovo_chrX", 'b', &o.vcf_denovo_chrX},
       {"vcf_denovo_chrX_detail", 'b', &o.vcf_denovo_chrX_detail}, {"vcf_posteriors", 'b', &o.vcf_posteriors},
       {"vcf_phase", 'b', &o.vcf_phase}, {"vcf_phase_minPQ", 'i', &o.vcf_phase_minPQ}, {"vcf_joint", 'b', &o.vcf_joint},
+      {"vcf_pedcheck", 's', &o.vcf_pedcheck},
   };
   auto assign = [](Flag& f, const char* v) {
     switch (f.kind) {
@@ -109,6 +110,7 @@ Options parse_command_line(int argc, char** argv) {
   if (o.vcf_posteriors && o.vcfInFile.empty()) throw FatalError("--vcf_posteriors needs --in_vcf\n");
   if (o.vcf_phase && o.vcfInFile.empty()) throw FatalError("--vcf_phase needs --in_vcf\n");
   if (o.vcf_joint && o.vcfInFile.empty()) throw FatalError("--vcf_joint needs --in_vcf\n");
+  if (!o.vcf_pedcheck.empty() && o.vcfInFile.empty()) throw FatalError("--vcf_pedcheck needs --in_vcf\n");
   if (o.vcf_phase_minPQ_given) {
     if (!o.vcf_phase) throw FatalError("--vcf_phase_minPQ needs --vcf_phase\n");
     if (o.vcf_phase_minPQ < 0 || o.vcf_phase_minPQ > 99) throw FatalError("--vcf_phase_minPQ takes a quality from 0 to 99\n");

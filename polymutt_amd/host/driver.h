@@ -61,6 +61,10 @@ struct Options {
   // its family's most probable joint (Mendelian-consistent) assignment and the log10 posterior of that assignment
   // (pm_engine_set_vcf_joint); GT stays the marginal call; combines freely with the other --vcf_ flags
   bool vcf_joint = false;
+  // --vcf_pedcheck FILE (with --in_vcf): at the end of the run FILE gets, for every non-founder, the log10 likelihood ratio of
+  // each stated parent link against an unrelated one, summed over the run's autosomal records (pm_engine_set_vcf_pedcheck);
+  // the VCF output and stdout do not change; combines freely with the other --vcf_ flags
+  std::string vcf_pedcheck;
   std::string cmd;
   pm_params params() const;
 };
@@ -144,6 +148,10 @@ class SiteEvaluator {
   // --vcf_joint: the same pair for the joint call plane (pm_engine_set_vcf_joint / pm_engine_vcf_joint)
   virtual void set_vcf_joint(bool on) { (void)on; throw FatalError("--vcf_joint is not supported by this evaluator\n"); }
   virtual int vcf_joint(pm_vcf_joint* out) { (void)out; throw FatalError("--vcf_joint is not supported by this evaluator\n"); }
+  // --vcf_pedcheck: set_vcf_pedcheck once, before the first batch; vcf_pedcheck, with no batch in flight, hands out the sums
+  // over every batch so far, added over the evaluator's engines (pm_engine_set_vcf_pedcheck / pm_engine_vcf_pedcheck)
+  virtual void set_vcf_pedcheck(bool on) { (void)on; throw FatalError("--vcf_pedcheck is not supported by this evaluator\n"); }
+  virtual void vcf_pedcheck(std::vector<pm_vcf_pedcheck>& out) { (void)out; throw FatalError("--vcf_pedcheck is not supported by this evaluator\n"); }
   // Host memory for the batch buffers (the engine: page-locked, for asynchronous copies)
   virtual void* host_alloc(size_t bytes);
   virtual void host_free(void* p);

@@ -169,6 +169,24 @@ class EngineEvaluator : public SiteEvaluator {
     check(pm_engine_vcf_joint(last_, &n, out));
     return n;
   }
+  void set_vcf_pedcheck(bool on) override {
+    for (auto* e : eng_) check(pm_engine_set_vcf_pedcheck(e, on ? 1 : 0));
+  }
+  void vcf_pedcheck(std::vector<pm_vcf_pedcheck>& out) override {   // (integer sums: the engines' order does not matter)
+    out.clear();
+    std::vector<pm_vcf_pedcheck> one;
+    for (auto* e : eng_) {
+      int32_t k = 0;
+      check(pm_engine_vcf_pedcheck(e, &k, nullptr));
+      one.resize((size_t)k);
+      if (k) check(pm_engine_vcf_pedcheck(e, &k, one.data()));
+      if (out.empty()) { out = one; continue; }
+      for (int i = 0; i < k; i++) {
+        out[i].n += one[i].n;
+        for (int h = 0; h < 3; h++) out[i].q[h] += one[i].q[h];
+      }
+    }
+  }
   void* host_alloc(size_t bytes) override {
     void* p = nullptr;
     if (pm_host_alloc(bytes ? bytes : 1, &p) != PM_OK || !p) return SiteEvaluator::host_alloc(bytes);   // pageable fallback

@@ -288,6 +288,31 @@ double bits2d(int64_t v) { double d; memcpy(&d, &v, 8); return d; }
 int64_t d2bits(double d) { int64_t v; memcpy(&v, &d, 8); return v; }
 }  // namespace
 
+// --vcf_pedcheck: the report, one line per non-founder in the pedigree's order (families by id, a family's founders before
+// their descendants: the order of the engine's persons).  LLR = q * 2^-28; SUSPECT names the links whose LLR is negative.
+static void write_pedcheck(const std::string& path, const Pedigree& ped, const std::vector<pm_vcf_pedcheck>& pc) {
+  FILE* f = fopen(path.c_str(), "w");
+  if (!f) throw FatalError("Open pedigree check file " + path + " failed!\n");
+  fprintf(f, "#polymutt pedcheck v1: log10 LR of each stated parent link against an unrelated one, summed over N_SITES autosomal "
+             "records\nFAMILY\tPERSON\tFATHER\tMOTHER\tN_SITES\tLLR_FATHER\tLLR_MOTHER\tLLR_BOTH\tSUSPECT\n");
+  static const char* const link[3] = {"father", "mother", "both"};
+  for (const pm_vcf_pedcheck& c : pc) {
+    const int p = c.person;
+    size_t fam = 0;
+    while (fam + 1 < ped.families.size() && ped.fam_start[fam + 1] <= p) fam++;
+    double llr[3];
+    std::string suspect;
+    for (int h = 0; h < 3; h++) {
+      llr[h] = c.n ? ldexp((double)c.q[h], -28) : 0.0;
+      if (llr[h] < 0) suspect += (suspect.empty() ? "" : ",") + std::string(link[h]);
+    }
+    fprintf(f, "%s\t%s\t%s\t%s\t%lld\t%.2f\t%.2f\t%.2f\t%s\n", ped.families[fam].famid.c_str(), ped.column_pid[p].c_str(),
+            ped.column_pid[ped.father[p]].c_str(), ped.column_pid[ped.mother[p]].c_str(), (long long)c.n, llr[0], llr[1], llr[2],
+            suspect.empty() ? "." : suspect.c_str());
+  }
+  fclose(f);
+}
+
 // Sharded (comm->world > 1): rank R analyses the records whose lines start in its slice of the body's bytes
 // (uncompressed offsets; gzip input is re-inflated up to the slice, never parsed) and writes their records to
 // <out>.part<R>.  Cross-record state is handed over explicitly: the FORMAT indices come from a pre-scan of the
@@ -403,6 +428,8 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
   const bool vj = opt.vcf_joint;
   if (vj) eval.set_vcf_joint(true);
   const pm_vcf_joint no_joint = {0.f, 255, {0, 0, 0}};
+  const bool vpc = !opt.vcf_pedcheck.empty();
+  if (vpc) eval.set_vcf_pedcheck(true);
   const int B = std::max(1, opt.batch);
   // Two batches: the main thread reads, classifies and parses records into one while the flusher thread runs the
   // engine on the other, formats its records and hands their text to the writer thread.  A batch's PL rows are in
@@ -1060,8 +1087,11 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     tm[5] += now() - tw;
   }
   tm[6] = now() - tm[6];
+  std::vector<pm_vcf_pedcheck> pedcheck;   // --vcf_pedcheck: this process's sums, over its engines
+  if (vpc && !stuck) eval.vcf_pedcheck(pedcheck);
   if (!sharded) {
     fclose(out);
+    if (vpc) write_pedcheck(opt.vcf_pedcheck, ped, pedcheck);
     if (bad_allele) fprintf(stderr, "%d biallelic records with non-ACGT alleles were skipped\n", bad_allele);
     return 0;
   }
@@ -1145,6 +1175,30 @@ int run_polymutt_vcf(const Options& opt, const Pedigree& ped, SiteEvaluator& eva
     int64_t one = 1;
     std::vector<int64_t> all(N);
     comm->allgather(&one, 1, all.data());
+  }
+  if (vpc) {   // --vcf_pedcheck: one more exchange, every rank's int64 sums; the lead adds them and writes the report
+    size_t k = 0;   // the non-founders: every rank sends as many words, a rank that met a stuck Brent zeros
+    for (int p = 0; p < np; p++) k += ped.father[p] >= 0 ? 1 : 0;
+    const bool have = pedcheck.size() == k;
+    if (!have && !stuck) throw FatalError("--vcf_pedcheck: the engine and the pedigree disagree on the non-founders\n");
+    const size_t W = 4 * k + 1;
+    std::vector<int64_t> mine(W, 0), all((size_t)N * W);
+    for (size_t i = 0; i < k && have; i++) {
+      mine[4 * i] = pedcheck[i].n;
+      for (int h = 0; h < 3; h++) mine[4 * i + 1 + h] = pedcheck[i].q[h];
+    }
+    mine[4 * k] = have ? 1 : 0;   // this rank's sums are complete
+    comm->allgather(mine.data(), (int32_t)W, all.data());
+    bool complete = have;
+    for (int q = 0; q < N; q++) complete = complete && all[(size_t)q * W + 4 * k] == 1;
+    if (R == 0 && stuck_rank < 0 && complete) {   // (the report is written only when every rank's run finished)
+      for (int q = 1; q < N; q++)
+        for (size_t i = 0; i < k; i++) {
+          pedcheck[i].n += all[(size_t)q * W + 4 * i];
+          for (int h = 0; h < 3; h++) pedcheck[i].q[h] += all[(size_t)q * W + 4 * i + 1 + h];
+        }
+      write_pedcheck(opt.vcf_pedcheck, ped, pedcheck);
+    }
   }
   if (R != 0) return stuck_rank >= 0 ? 1 : 0;   // (the lead prints the FATAL text once)
   FILE* fin = fopen(opt.vcfOutFile.c_str(), "w");

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Cost of one output plane of vcf_mode engines -- `--plane posteriors` (pm_engine_set_vcf_posteriors), `phase`
-(pm_engine_set_vcf_phase) or `joint` (pm_engine_set_vcf_joint): device-resident batches (pm_engine_synth, (ref, alt =
+(pm_engine_set_vcf_phase) or `joint` (pm_engine_set_vcf_joint) -- or of the pedigree check, `--plane pedcheck`
+(pm_engine_set_vcf_pedcheck: no plane, sums per non-founder; timed next to the phase and the joint plane): device-resident batches (pm_engine_synth, (ref, alt =
 transition) per site as bench.py --vcf makes them), engines in flight as in bench.py.
 
 Two geometries, each timed with the feature off and on in one session (the joint plane also with the phase plane on
@@ -66,6 +67,14 @@ def joint_stats(eng):
         "plane_mean_lp": float(lp[g != 255].mean()) if (g != 255).any() else None}
 
 
+def pedcheck_stats(eng):
+    pc = eng.vcf_pedcheck()
+    return int(pc.n.max(initial=0)), int(len(pc.person) * pm.VCF_PEDCHECK_DTYPE.itemsize), {
+        "non_founders": int(len(pc.person)), "all_counted_alike": bool((pc.n == pc.n.max(initial=0)).all()),
+        "share_all_links_supported": float((pc.llr > 0).all(axis=1).mean()) if len(pc.person) else None,
+        "sums_sha256": hashlib.sha256(pc.n.tobytes() + pc.q.tobytes()).hexdigest()}
+
+
 # per plane: the engine's setter, the plane's figures after a batch, the extra pass per geometry, what else is timed
 # (mode -> the JSON prefix of its keys) and whether the profile carries the two keys the first tool did not write
 PLANES = {
@@ -77,7 +86,11 @@ PLANES = {
     "joint": {"setter": "set_vcf_joint", "stats": joint_stats, "also": {"phase": "phase_"}, "notes": True,
               "extra_pass": {"config5": "k_vcf_joint_lean",
                              "ext10": "k_vcf_joint_nuc (no work) + k_vcf_joint_es (one sum peel, one max peel and its backtrack per family)"}},
+    "pedcheck": {"setter": "set_vcf_pedcheck", "stats": pedcheck_stats, "also": {"phase": "phase_", "joint": "joint_"}, "notes": True,
+                 "extra_pass": {"config5": "k_vcf_pedcheck_lean",
+                                "ext10": "k_vcf_pedcheck_es (four generic reference-order peels per child)"}},
 }
+OUTPUT_PLANES = ("posteriors", "phase", "joint")   # what --digest-planes covers (the parent commit's package has these)
 
 
 def pedigree(shape, families):
@@ -116,8 +129,8 @@ def digest(sites, seed, planes):
         res, calls = eng.run_vcf(block, href)
         out[label] = {"sites": sites, "rows": int(len(calls)), "sha256": sha(res, calls)}
         if planes:
-            for p in PLANES.values():
-                getattr(eng, p["setter"])(True)
+            for k in OUTPUT_PLANES:
+                getattr(eng, PLANES[k]["setter"])(True)
             res, calls = eng.run_vcf(block, href)
             out[label]["planes_on_sha256"] = sha(res, calls)
             out[label]["planes"] = {"posteriors": sha(eng.vcf_posteriors()), "phase": sha(eng.vcf_phase()), "joint": sha(*eng.vcf_joint())}
